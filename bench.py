@@ -6,11 +6,17 @@ BASELINE.json metric "Gatys iters/sec at 512x512 + fast_st images/sec at
 gatys_st 512x512 single image, Adam iterations = forward + backward + Adam update
 of the image, one hipGraph replay each).  Gatys optimises one image serially, so
 ranks run independent replicas and the job rate is the sum.
-The fast_st leg (config 4 shape: 256x256, per-GPU batch 8, data-parallel with one
-RCCL all-reduce of the flat ImageTransformNet gradient per step) is reported in
-the same line under "fast_st".  Inputs are resident in HBM before timing.
+Inputs are resident in HBM before timing.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does what that headline figure needs and no more: set-up, warm-up, the K
+timed steps, the `--dump-outputs` files if asked for, and the result line.  `--full`
+adds every other leg to the same line: the box calibration, config 2's 500-iteration
+run, the roofline / Gram kernel timings, the L-BFGS leg, the fast_st legs (config 4
+shape: 256x256, per-GPU batch 8, data-parallel with one RCCL all-reduce of the flat
+ImageTransformNet gradient per step; under "fast_st"), the video / convert / loader
+legs and the CPU baseline.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...    (one rank per GPU)
 """
 from __future__ import annotations
@@ -26,6 +32,7 @@ import time
 
 import socket
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -102,6 +109,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beyond the headline Gatys window (the options below "
+                         "select among those legs and matter only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed Gatys step computed (rank 0) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--fast-batch", type=int, default=8, help="fast_st images per GPU")
     ap.add_argument("--fast-steps", type=int, default=50, help="timed fast_st train steps")
     ap.add_argument("--fast-b64-steps", type=int, default=10,
@@ -217,6 +230,23 @@ def box_calibration(dev):
                     "moved), HIP events, best of 3 x 10; same process, before the legs"}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """`path`/<name>.npy in float32, at most DUMP_BYTES in all: an array over its equal
+    share of that is cut to a fixed, seeded sample of its elements (the same ones in every
+    run, in index order)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def gatys_leg(args, world, rank, dev):
     H = args.size
     style = torch.from_numpy(W.synthetic_image(1000 + rank, (1, 3, H, H))).to(dev)
@@ -239,8 +269,26 @@ def gatys_leg(args, world, rank, dev):
         torch.cuda.synchronize(dev)
         first_replay_ms = (time.perf_counter() - t0) * 1e3
     nwarm = warm(eng.step, args.warmup, dev, world)
+    # the warm-up's length follows the clock, so the optimisation is put back at its start
+    # (image, Adam moments, step count -- all the state an iteration carries over): the K
+    # timed steps are then steps 1..K of the same run in every process, and what the last
+    # one leaves can be compared between two builds
+    eng.x.copy_(eng.content)
+    eng.m.zero_()
+    eng.v.zero_()
+    eng.step_dev.zero_()
     dt = timed(eng.step, args.steps, world, dev)
     rate = world * args.steps / dt
+    # what a caller of step() / run() holds after the last timed step: the image, its
+    # gradient, the weighted total and the seven losses
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = {"image": eng.x, "grad": eng.grad, "total": eng.total.reshape(1),
+                   "losses": eng.losses()}
+        outputs = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in outputs.items()}
+    if not args.full:
+        return dict(rate=rate, dt=dt, loss=float(eng.total), run=None, outputs=outputs,
+                    first_replay_ms=first_replay_ms, warm_calls=nwarm, kernel=None, gram=None)
     run = None
     if args.gatys_run_iters > 0:
         # BASELINE config 2 as written: one gatys_st run of 500 Adam iterations
@@ -337,7 +385,7 @@ def gatys_leg(args, world, rank, dev):
     # phase, 1 the fp32-MFMA phase
     p2 = 1 if ca is None or N.knob("STX_P2_SPLIT", "1") == "0" else 3
     return dict(rate=rate, dt=dt, loss=loss, run=run, first_replay_ms=first_replay_ms,
-                warm_calls=nwarm,
+                warm_calls=nwarm, outputs=outputs,
                 kernel=dict(fwd_ms=fwd_ms, gflop=gf,
                                                          dg_kernel=DG_KERNEL.format(p2),
                                                          gflop_conv=gf_conv, tflops=achieved,
@@ -721,20 +769,23 @@ def main():
             print(json.dumps({"fast_st_images_per_s": round(fs["rate"], 3),
                               "ms_per_step": round(1e3 * fs["dt"] / fs["steps"], 3)}))
         return
-    box = box_calibration(dev)
+    full = args.full
+    box = box_calibration(dev) if full else None
     g = gatys_leg(args, world, rank, dev)
-    lb = gatys_lbfgs_leg(args, world, rank, dev) if args.lbfgs_steps > 0 else None
-    fs = None if args.skip_fast else fast_st_leg(args, world, rank, dev)
+    if g["outputs"] is not None:
+        dump_outputs(args.dump_outputs, g["outputs"])
+    lb = gatys_lbfgs_leg(args, world, rank, dev) if full and args.lbfgs_steps > 0 else None
+    fs = fast_st_leg(args, world, rank, dev) if full and not args.skip_fast else None
     fs64 = None
-    if not args.skip_fast and world == 1 and args.fast_b64_steps > 0:
+    if fs is not None and world == 1 and args.fast_b64_steps > 0:
         # at 1 GPU the config-4 global batch of 64 on one device
         fs64 = fast_st_leg(args, world, rank, dev, B=64, steps=args.fast_b64_steps)
     vid = conv = None
-    if not args.skip_infer:
+    if full and not args.skip_infer:
         vid = video_leg(args, world, rank, dev)
         conv = convert_leg(args, world, rank, dev)
     ld = None
-    if args.loader_images > 0 and not args.skip_infer:
+    if full and args.loader_images > 0 and not args.skip_infer:
         # every rank runs its own loader on its share of the node's CPUs (the worker count
         # follows LOCAL_WORLD_SIZE); the line reports the slowest rank
         ld = coco_loader_leg(args, dev)
@@ -743,11 +794,9 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             ld["rate_min_rank"] = float(t.item())
     cpu = None
-    if rank == 0 and world == 1 and not args.skip_cpu:
+    if full and rank == 0 and world == 1 and not args.skip_cpu:
         cpu = cpu_baseline(args)
     if rank == 0:
-        k = g["kernel"]
-        traffic_bytes, traffic_src, traffic_rec = pmc_traffic()
         res = {
             "metric": METRIC,
             "value": round(g["rate"], 3),
@@ -756,6 +805,7 @@ def main():
             "devices": 1 if same else world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": full,
             "ms_per_step": round(1e3 * g["dt"] / args.steps, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -767,6 +817,11 @@ def main():
                                    "per GPU (replicas)",
                        "image": args.size, "batch": 1, "parallelism": f"replicas{world}",
                        "graph": not args.no_graph},
+        }
+        # --full: the kernel timings of gatys_leg, the CPU baseline and the box calibration
+        k = g["kernel"]
+        traffic_bytes, traffic_src, traffic_rec = pmc_traffic() if full else (None, None, None)
+        res.update({} if not full else {
             "roofline": {
                 "bound": "mfma",
                 "kernel": f"{ROOFLINE_KERNEL} (conv1_2 forward, 64->64 3x3 @ "
@@ -843,8 +898,8 @@ def main():
             },
             "cpu_baseline": cpu,
             "box": box,
-            "gatys_loss": g["loss"],
-        }
+        })
+        res["gatys_loss"] = g["loss"]
         if g.get("first_replay_ms") is not None:
             # (untimed: the captured graph's first replay, before the W - 1 other warm-ups)
             res["gatys_first_replay_ms"] = round(g["first_replay_ms"], 3)

@@ -38,6 +38,7 @@ REF = "/root/reference"
 GOLDEN = os.path.join(REPO, "tests", "golden")
 sys.path.insert(0, REPO)
 
+from oracle import golden_io  # noqa: E402
 from oracle import reference_cpu as O  # noqa: E402
 from styletransfer_amd import weights as W  # noqa: E402
 
@@ -673,7 +674,7 @@ def main():
             continue
         out = fn()
         if not args.check_only:
-            np.savez_compressed(os.path.join(GOLDEN, f"{name}.npz"), **out)
+            golden_io.save(GOLDEN, name, out)  # (split into <name>.<i>.npz above 1 MiB)
         print(f"{name}: ok ({len(out)} arrays)")
     # weight generator pin (hash PRNG) — checksum of the generated tensors
     vgg = W.vgg19_synthetic(VGG_SEED, 5)

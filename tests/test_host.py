@@ -129,6 +129,33 @@ def test_imshow_bytes_match_reference(tmp_path):
     assert np.array_equal(np.asarray(Image.open(p)), d["imshow_out"])
 
 
+def test_golden_io_split_round_trip(tmp_path):
+    """oracle/golden_io.py: a fixture over the file-size limit is written as several files,
+    each within it, and loads back as the same arrays byte for byte (an incompressible
+    array larger than one file is cut; scalars and small arrays ride along); a small one
+    stays a single <name>.npz.  No fixture file of the suite is above 1 MiB."""
+    from oracle import golden_io
+    rng = np.random.default_rng(5)
+    arrays = {"n": np.asarray(3), "big": rng.random((3, 401, 257)).astype(np.float32),
+              "bits": rng.integers(0, 256, 700_001, dtype=np.uint8), "s": np.float64(0.25),
+              "m": rng.random((2, 64, 65))}
+    paths = golden_io.save(str(tmp_path), "case", arrays)
+    assert len(paths) > 1 and all(os.path.getsize(p) <= golden_io.LIMIT for p in paths)
+    back = golden_io.load(str(tmp_path), "case")
+    assert list(back) == list(arrays)
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        assert back[k].dtype == a.dtype and back[k].shape == a.shape
+        assert back[k].tobytes() == a.tobytes(), k
+    small = {"a": np.arange(5), "b": np.float32(1.5)}
+    assert [os.path.basename(p) for p in golden_io.save(str(tmp_path), "case", small)] == ["case.npz"]
+    assert sorted(os.listdir(tmp_path)) == ["case.npz"]  # (the split files were replaced)
+    assert np.array_equal(golden_io.load(str(tmp_path), "case")["a"], np.arange(5))
+    with pytest.raises(FileNotFoundError):
+        golden_io.load(str(tmp_path), "absent")
+    assert all(os.path.getsize(os.path.join(GOLDEN, f)) <= 1 << 20 for f in os.listdir(GOLDEN))
+
+
 def test_latest_weights_lexicographic(tmp_path, monkeypatch):
     from styletransfer_amd import constants, network
     mdir = tmp_path / "data" / "models"

@@ -7,12 +7,13 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from oracle import golden_io
 from oracle import reference_cpu as O
 from styletransfer_amd import weights as W
 
 
 def g(name):
-    return np.load(os.path.join(GOLDEN, f"{name}.npz"))
+    return golden_io.load(GOLDEN, name)
 
 
 def rel(a, b):

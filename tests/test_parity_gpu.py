@@ -17,6 +17,7 @@ import torch
 
 import forced_ref as R
 from conftest import GOLDEN
+from oracle import golden_io
 from styletransfer_amd import network, ops
 from styletransfer_amd import vgg as V
 from styletransfer_amd import weights as W
@@ -25,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 
 def g(name):
-    return np.load(os.path.join(GOLDEN, f"{name}.npz"))
+    return golden_io.load(GOLDEN, name)
 
 
 def rel(a, b):

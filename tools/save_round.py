@@ -1,4 +1,4 @@
-"""Copy the tools/gpu_r4.sh outputs gpurun_out/<tag>_* into profiles/<tag>_*: the bench
+"""Copy the tools/gpu_r4.sh outputs $STX_OUT/<tag>_* into profiles/<tag>_*: the bench
 line, the rocprofv3 --stats summaries of the bench's Gatys-Adam legs, its L-BFGS leg and
 its fast_st leg, the per-iteration Gatys breakdown, and the per-grid durations of the
 roofline and dominant kernels (same trace).  The calibrated PMC record is written by
@@ -11,7 +11,7 @@ import subprocess
 import sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r3"
-G = "gpurun_out"
+G = os.environ.get("STX_OUT", "bench_out")  # (where tools/gpu_r4.sh wrote)
 shutil.copy(f"{G}/{tag}_bench.json", f"profiles/{tag}_bench.json")
 shutil.copy(f"{G}/{tag}_prof/run_kernel_stats.csv", f"profiles/{tag}_bench_kernel_stats.csv")
 shutil.copy(f"{G}/{tag}_profl/run_kernel_stats.csv", f"profiles/{tag}_lbfgs_kernel_stats.csv")
@@ -21,7 +21,7 @@ if os.path.exists(f"{G}/{tag}_pmc.json"):
 br = subprocess.check_output([sys.executable, "tools/iter_breakdown.py",
                               f"{G}/{tag}_prof/run_kernel_trace.csv"], text=True)
 open(f"profiles/{tag}_gatys512_iteration_breakdown.txt", "w").write(
-    "rocprofv3 --kernel-trace of `python3 bench.py --skip-cpu --skip-fast --skip-infer "
+    "rocprofv3 --kernel-trace of `python3 bench.py --full --skip-cpu --skip-fast --skip-infer "
     "--lbfgs-steps 0` "
     "(tools/iter_breakdown.py: kernels between consecutive Adam launches, last 20 "
     "iterations)\n" + br)
