@@ -907,7 +907,7 @@ conv3x3_f16x3_v2_kernel(stx_conv_params p, int tiles_x, int ntiles) {
   const bool half_m = (PAR || UPP) && co0 + 32 >= p.cout;
   const int ex = amax_exp(read_amax(p.in_amax));
   const int ew = amax_exp(read_amax(p.w_amax)) + (UPP ? 2 : 0);  // (UPP: |W'| <= 4 max|w|)
-  const float sx = __builtin_ldexpf(1.f, 15 - ex);
+  [[maybe_unused]] const float sx = __builtin_ldexpf(1.f, 15 - ex);  // (DIAG=1: no split)
   const float descale = __builtin_ldexpf(1.f, ex + ew - 30);
 
   const int plane_in = p.h * p.w;
@@ -1380,16 +1380,6 @@ static int launch16v2(const stx_conv_params& p, hipStream_t st) {
                          tiles_x, ntiles);
       return check_launch("stx_conv2d(f16x3 v2, 128 couts)");
     }
-#ifdef STX_AB  // STX_FORCE_WM2=1: 8-wave 128-cout blocks on 64 x 4 tiles without the Gram (A/B)
-  if constexpr (NI == 2 && TW == 64 && (LM == STX_IN_RAW || LM == STX_IN_RELU))
-    if (STX_KNOB("STX_FORCE_WM2", 0) && p.cout % 128 == 0 && !p.mask && !p.accumulate &&
-        !p.acc_scale && !p.up_dp && !p.pool_sum && !p.gram_part && !p.aux) {
-      dim3 g2(ntiles, p.cout / 128, p.n);
-      hipLaunchKernelGGL((conv3x3_f16x3_v2_kernel<TW, LM, 0, NI, 2>), g2, dim3(512), 0, st, p,
-                         tiles_x, ntiles);
-      return check_launch("stx_conv2d(f16x3 v2, 128 couts, forced)");
-    }
-#endif
   if constexpr (LM == STX_IN_DILATE2 && TW == 64 && NI == 2)
     if (p.mask || p.accumulate || p.acc_scale || p.up_dp || p.pool_out || p.pool_sum ||
         p.gram_part || (p.aux && p.relu_out)) {

@@ -567,41 +567,30 @@ static void launch_gb(const Gb16& p, int nimg, hipStream_t st) {
   launch_gb1<C, NB, false, false, CQ, PF, AXT>(p, nimg, st);
 }
 
-// C in {64, 128, 256} (256: no up_dp), h even, w % 16 == 0, dense channels; the caller
-// (stx_conv2d's split 1x1 mode) checks the rest of the contract.
-template <int C, int NB, int CQ>
+// the first version's kernel: C = 64 with aux, and C = 128
+template <int C, int NB, bool AUX>
 static void launch_gb_v1(const Gb16& p, int nimg, hipStream_t st) {
   constexpr int NW = (C == 128 && NB == 1) ? 8 : 4;
   constexpr int slots = NW == 8 ? 256 : 512;  // resident blocks (2048 waves)
-  constexpr int NQ = C / CQ;
   const int units = (p.h / 2) * (p.w / (16 * NB));
-  const dim3 grid(std::max(1, std::min((units + NW - 1) / NW, std::max(1, slots / (nimg * NQ)))),
-                  nimg * NQ);
-  if (p.aux)
-    hipLaunchKernelGGL((gram_bwd16_v1_kernel<C, NB, true, NW, CQ>), grid, dim3(64 * NW), 0, st, p);
-  else
-    hipLaunchKernelGGL((gram_bwd16_v1_kernel<C, NB, false, NW, CQ>), grid, dim3(64 * NW), 0, st, p);
+  const dim3 grid(std::max(1, std::min((units + NW - 1) / NW, std::max(1, slots / nimg))), nimg);
+  hipLaunchKernelGGL((gram_bwd16_v1_kernel<C, NB, AUX, NW>), grid, dim3(64 * NW), 0, st, p);
 }
 
 // C in {64, 128, 256} (256: no up_dp), h even, w % 16 == 0, dense channels; the caller
 // (stx_conv2d's split 1x1 mode) checks the rest of the contract.
 int gram_bwd16_launch(const Gb16& p, int nimg, int c, hipStream_t st) {
   static const int nb_env = STX_KNOB("STX_GB_NB", 0);
-  // STX_GB_V1=1: the run-time-branch loop schedule (A/B)
-  static const bool v1 = STX_KNOB("STX_GB_V1", 0) != 0;
   const bool two = (nb_env ? nb_env : 2) == 2 && p.w % 32 == 0;
   if (c == 64) {
-    if (v1 || p.aux)
-      two ? launch_gb_v1<64, 2, 64>(p, nimg, st) : launch_gb_v1<64, 1, 64>(p, nimg, st);
+    if (p.aux)
+      two ? launch_gb_v1<64, 2, true>(p, nimg, st) : launch_gb_v1<64, 1, true>(p, nimg, st);
     else
       two ? launch_gb<64, 2, 64, true, 2>(p, nimg, st) : launch_gb<64, 1, 64, true, 2>(p, nimg, st);
   } else if (c == 128) {
-    launch_gb_v1<128, 1, 128>(p, nimg, st);
+    p.aux ? launch_gb_v1<128, 1, true>(p, nimg, st) : launch_gb_v1<128, 1, false>(p, nimg, st);
   } else {  // C = 256 (conv3_1): no fused unpool
-    if (v1)
-      launch_gb_v1<256, 1, 64>(p, nimg, st);
-    else
-      launch_gb<256, 1, 64, false, 2>(p, nimg, st);
+    launch_gb<256, 1, 64, false, 2>(p, nimg, st);
   }
   return check_launch("stx_conv2d(gram backward, split 1x1)");
 }

@@ -416,9 +416,9 @@ __device__ __forceinline__ void gram_f16_tile(const float* __restrict__ z, float
 }
 #undef MF16
 
-// Whole-triangle split Gram for C = 128 / 256 (the conv2_x / conv3_1 taps): a block
+// Whole-triangle split Gram for C = 128 (the conv2_x taps): a block
 // takes a pixel range of one image and ALL 32 x 32 blocks of the upper triangle of
-// G (10 / 36 of them), so z is read exactly once (the 64 x 64-tile kernel above reads
+// G (10 of them), so z is read exactly once (the 64 x 64-tile kernel above reads
 // every row (nt + 1) / 2 times).  Per chunk of 64 pixels the C x 64 slab is split
 // into fp16 hi/lo planes in LDS ([plane][channel][pixel], pitch 72 halves: the 16-B
 // fragment reads of 16 lanes hit distinct banks) -- once per element instead of once
@@ -428,11 +428,12 @@ __device__ __forceinline__ void gram_f16_tile(const float* __restrict__ z, float
 // lower-left quadrant).
 // MSE: also the content/feature sums of (z - cz)^2 and (relu z - relu cz)^2 over the
 // block's pixels (the pass over z the content loss needs anyway): mparts[2 blk + 0/1]
-template <int C, bool MSE = false>
+template <bool MSE = false>
 __global__ void __launch_bounds__(256, 1)
 gram_tri_f16_kernel(const float* __restrict__ z, float* __restrict__ ws, int hw, int nsplit,
                     int split_len, const float* __restrict__ z_amax,
                     const float* __restrict__ cz = nullptr, float* __restrict__ mparts = nullptr) {
+  constexpr int C = 128;
   constexpr int NB = C / 32;                 // 32-row blocks per side
   constexpr int NBLK = NB * (NB + 1) / 2;    // upper-triangle blocks
   constexpr int PER = (NBLK + 3) / 4;        // per wave
@@ -562,7 +563,6 @@ gram_tri_f16_kernel(const float* __restrict__ z, float* __restrict__ ws, int hw,
 // 128^2); the 4-wave triangle kernel (1 wave per SIMD, 9 accumulator blocks per wave)
 // was slower still.  Partials: the 64 x 64-tile layout gram_finalize reads.
 constexpr int T256_PX = 32;  // pixels per chunk
-template <bool STAGED>
 __global__ void __launch_bounds__(512, 1)
 gram_tri256_kernel(const float* __restrict__ z, float* __restrict__ ws, int hw, int nsplit,
                    int split_len, const float* __restrict__ z_amax) {
@@ -688,50 +688,34 @@ gram_tri256_kernel(const float* __restrict__ z, float* __restrict__ ws, int hw, 
   }
   // partials in the 64 x 64-tile layout [b][tile][split][64][64] (diagonal tiles with the
   // mirrored lower-left quadrant)
-  if constexpr (STAGED) {
-    // each wave's 32 x 32 block through its own LDS region (pitch 40 floats: the two lane
-    // halves' rows land 32 banks apart), then 16-B stores: 8 rows x 128 B per store
-    // instruction instead of 2 x 128 B
-    constexpr int PITCH = 40;
-    float* reg = reinterpret_cast<float*>(lds) + wave * 32 * PITCH;
-    __syncthreads();  // the last chunk's fragment reads are done
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      if (q >= cnt) break;
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        reg[((r & 3) + 8 * (r >> 2) + 4 * h) * PITCH + l32] = acc[q][r] * inv2;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS stores landed
-      const int I = bi[q] >> 1, J = bj[q] >> 1, qi = bi[q] & 1, qj = bj[q] & 1;
-      float* out = ws + (((size_t)b * NTU + tile_index(I, J, NT)) * nsplit + split) * (GT * GT);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int row = (lane >> 3) + 8 * k, c4 = lane & 7;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(reg + row * PITCH + 4 * c4);
-        *reinterpret_cast<f32x4*>(out + (qi * 32 + row) * GT + qj * 32 + 4 * c4) = v;
-        if (I == J && qi != qj) {  // mirror: row `row` of the transposed block
-          f32x4 m;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) m[e] = reg[(4 * c4 + e) * PITCH + row];
-          *reinterpret_cast<f32x4*>(out + (qj * 32 + row) * GT + qi * 32 + 4 * c4) = m;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next stores
-    }
-    return;
-  }
+  // each wave's 32 x 32 block through its own LDS region (pitch 40 floats: the two lane
+  // halves' rows land 32 banks apart), then 16-B stores: 8 rows x 128 B per store
+  // instruction instead of 2 x 128 B
+  constexpr int PITCH = 40;
+  float* reg = reinterpret_cast<float*>(lds) + wave * 32 * PITCH;
+  __syncthreads();  // the last chunk's fragment reads are done
 #pragma unroll
   for (int q = 0; q < PER; ++q) {
     if (q >= cnt) break;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      reg[((r & 3) + 8 * (r >> 2) + 4 * h) * PITCH + l32] = acc[q][r] * inv2;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS stores landed
     const int I = bi[q] >> 1, J = bj[q] >> 1, qi = bi[q] & 1, qj = bj[q] & 1;
     float* out = ws + (((size_t)b * NTU + tile_index(I, J, NT)) * nsplit + split) * (GT * GT);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-      const float v = acc[q][r] * inv2;
-      out[(qi * 32 + row) * GT + qj * 32 + l32] = v;
-      if (I == J && qi != qj) out[(qj * 32 + l32) * GT + qi * 32 + row] = v;  // mirror
+    for (int k = 0; k < 4; ++k) {
+      const int row = (lane >> 3) + 8 * k, c4 = lane & 7;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(reg + row * PITCH + 4 * c4);
+      *reinterpret_cast<f32x4*>(out + (qi * 32 + row) * GT + qj * 32 + 4 * c4) = v;
+      if (I == J && qi != qj) {  // mirror: row `row` of the transposed block
+        f32x4 m;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m[e] = reg[(4 * c4 + e) * PITCH + row];
+        *reinterpret_cast<f32x4*>(out + (qj * 32 + row) * GT + qi * 32 + 4 * c4) = m;
+      }
     }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next stores
   }
 }
 
@@ -758,10 +742,7 @@ static int gram_tri_splits(int c, int hw, int b) {
 
 static bool gram_tri_on(int c, int hw) {
   static const bool on = STX_KNOB("STX_GRAM_TRI", 1) != 0;
-  // C = 256 @ 128^2 measured slower than the 64 x 64-tile kernel (36 vs 10 blocks of
-  // accumulators per block: 33-37 us vs 32 us with the finalize); STX_GRAM_TRI=2 forces it
-  static const bool all = STX_KNOB("STX_GRAM_TRI", 1) == 2;
-  return on && (c == 128 || (all && c == 256)) && hw % 64 == 0;
+  return on && c == 128 && hw % 64 == 0;
 }
 
 // grid (ntu * FSUB, B), 512 threads: 64 tile elements (16 lanes x float4, one 256-B
@@ -865,7 +846,7 @@ __device__ __forceinline__ void gram_finalize_body(
   __shared__ float part[FKL * (FEL + 1)];
   __shared__ float red[FNT / 64];
   // block (0, 0) also finalizes the content / feature MSE partials of a fused content
-  // pass (gram_tri_f16_kernel<128, true>): the launch a separate mse2 finalize would take
+  // pass (gram_tri_f16_kernel<true>): the launch a separate mse2 finalize would take
   if (mse_out && bx == 0 && by == 0) {
     float s = 0.f, sr = 0.f;
     for (int i = threadIdx.x; i < mse_nparts; i += FNT) {
@@ -1074,31 +1055,22 @@ static int gram_run(const float* z, int b, int c, int hw, float scale, float* g_
     nsplit = gram_tri_splits(c, hw, b);
     split_len = rup(cdiv(hw, nsplit), 64);
     nsplit = cdiv(hw, split_len);
-    if (c == 128 && mse && (reinterpret_cast<uintptr_t>(mse->content) & 15) == 0 &&
+    if (mse && (reinterpret_cast<uintptr_t>(mse->content) & 15) == 0 &&
         mse->parts_bytes >= (size_t)2 * b * nsplit * sizeof(float)) {
-      hipLaunchKernelGGL((gram_tri_f16_kernel<128, true>), dim3(nsplit, 1, b), dim3(256), 0, st,
+      hipLaunchKernelGGL(gram_tri_f16_kernel<true>, dim3(nsplit, 1, b), dim3(256), 0, st,
                          z, slabs, hw, nsplit, split_len, z_amax, mse->content, mse->parts);
       mse_fin = mse;  // finalized by the Gram finalize below
       mse_nparts = b * nsplit;
       mse = nullptr;  // done
-    } else if (c == 128)
-      hipLaunchKernelGGL(gram_tri_f16_kernel<128>, dim3(nsplit, 1, b), dim3(256), 0, st, z, slabs,
+    } else
+      hipLaunchKernelGGL(gram_tri_f16_kernel<false>, dim3(nsplit, 1, b), dim3(256), 0, st, z, slabs,
                          hw, nsplit, split_len, z_amax);
-#ifdef STX_AB  // C = 256 on the triangle kernel (measured slower; STX_GRAM_TRI=2)
-    else
-      hipLaunchKernelGGL(gram_tri_f16_kernel<256>, dim3(nsplit, 1, b), dim3(256), 0, st, z, slabs,
-                         hw, nsplit, split_len, z_amax);
-#endif
   } else if (f16 && gram_tri256_on(c, hw)) {
     nsplit = gram_tri256_splits(hw, b);
     split_len = rup(cdiv(hw, nsplit), T256_PX);
     nsplit = cdiv(hw, split_len);
-    if (STX_KNOB("STX_GRAM256_STAGE", 1))
-      hipLaunchKernelGGL(gram_tri256_kernel<true>, dim3(nsplit, 1, b), dim3(512), 0, st, z, slabs,
-                         hw, nsplit, split_len, z_amax);
-    else
-      hipLaunchKernelGGL(gram_tri256_kernel<false>, dim3(nsplit, 1, b), dim3(512), 0, st, z, slabs,
-                         hw, nsplit, split_len, z_amax);
+    hipLaunchKernelGGL(gram_tri256_kernel, dim3(nsplit, 1, b), dim3(512), 0, st, z, slabs, hw,
+                       nsplit, split_len, z_amax);
   } else if (f16) {
     hipLaunchKernelGGL(gram_partial_f16_kernel, dim3(nsplit * ntu, 1, b), dim3(256), 0, st, z,
                        slabs, c, hw, nsplit, split_len, z_amax);
@@ -1303,7 +1275,7 @@ extern "C" int stx_style_content_loss_deferred(const float* z, const float* targ
 // gparts: [b][ntu][nparts][64 x 64] (ntu = 1 for c <= 64, 3 for c = 128: the fused conv
 // epilogue tiles, stx_conv_params.gram_part); mse_parts (c = 128, the content tap): the
 // epilogue's 2 sums per block, b * nparts pairs, finalized into mse_out like
-// gram_tri_f16_kernel<128, true>'s
+// gram_tri_f16_kernel<true>'s
 static int from_parts_impl(const float* gparts, int nparts, const float* target, float* g_out,
                            float* coef, float* loss, int b, int c, int hw, int target_batched,
                            float weight, float diag_alpha, void* ws, size_t ws_bytes,

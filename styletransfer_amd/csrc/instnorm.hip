@@ -385,21 +385,25 @@ instnorm_bwd_reg_kernel(const float* __restrict__ dy, const float* __restrict__ 
   }
 }
 
-// Pipelined register variants for planes of exactly 4*NT*R4 floats (the ITN's 64^2
-// planes, 1024 of them at B = 8): a block walks PPB consecutive planes and issues the
-// next plane's loads before this plane's reductions and stores, so the chip's load and
-// store phases overlap instead of every block loading, reducing and storing in lockstep
-// (one-plane blocks all resident at once: 13 us for 34 MB).  Loads are unconditional
-// (exact plane size, compile-time residual / ReLU) so each wait covers one plane's loads.
-// Same arithmetic and reduction order per plane as the one-plane kernels (same bits).
-template <int NT, int R4, int PPB, bool RES>
-__global__ void __launch_bounds__(NT)
+// Pipelined register kernels for planes of exactly 4*PIPE_NT*PIPE_R4 = 64^2 floats (the
+// ITN's 64^2 planes, 1024 of them at B = 8): a block walks PIPE_PPB consecutive planes and
+// issues the next plane's loads before this plane's reductions and stores, so the chip's
+// load and store phases overlap instead of every block loading, reducing and storing in
+// lockstep (one-plane blocks all resident at once: 13 us for 34 MB).  Loads are
+// unconditional (exact plane size, compile-time residual / ReLU) so each wait covers one
+// plane's loads.  Same arithmetic and reduction order per plane as the one-plane kernels
+// (same bits).
+constexpr int PIPE_NT = 512, PIPE_R4 = 2, PIPE_PPB = 4;
+constexpr int PIPE_HW = 4 * PIPE_NT * PIPE_R4;
+
+template <bool RES>
+__global__ void __launch_bounds__(PIPE_NT)
 instnorm_fwd_pipe_kernel(const float* __restrict__ x, const float* __restrict__ res,
                          const float* __restrict__ gamma, const float* __restrict__ beta,
                          float* __restrict__ y, float* __restrict__ mean_out,
                          float* __restrict__ rstd_out, int c, float eps, int relu,
                          float* __restrict__ out_amax) {
-  constexpr int HW = 4 * NT * R4;
+  constexpr int NT = PIPE_NT, R4 = PIPE_R4, PPB = PIPE_PPB, HW = PIPE_HW;
   __shared__ float red[NT / 64];
   const int p0 = blockIdx.x * PPB;
   f32x4 xb[2][R4], rb[2][R4];
@@ -473,14 +477,14 @@ instnorm_fwd_pipe_kernel(const float* __restrict__ x, const float* __restrict__ 
   }
 }
 
-template <int NT, int R4, int PPB, bool RELU, bool RES>
-__global__ void __launch_bounds__(NT)
+template <bool RELU, bool RES>
+__global__ void __launch_bounds__(PIPE_NT)
 instnorm_bwd_pipe_kernel(const float* __restrict__ dy, const float* __restrict__ beta,
                          const float* __restrict__ x, const float* __restrict__ res,
                          const float* __restrict__ gamma, const float* __restrict__ mean,
                          const float* __restrict__ rstd, float* __restrict__ du,
                          float* __restrict__ parts, int c, float* __restrict__ out_amax) {
-  constexpr int HW = 4 * NT * R4;
+  constexpr int NT = PIPE_NT, R4 = PIPE_R4, PPB = PIPE_PPB, HW = PIPE_HW;
   __shared__ float red[NT / 64];
   const int p0 = blockIdx.x * PPB;
   f32x4 db[2][R4], xb[2][R4], rb[2][R4];
@@ -563,42 +567,23 @@ instnorm_bwd_pipe_kernel(const float* __restrict__ dy, const float* __restrict__
   }
 }
 
-// block shape of the planes between 4 x 256 x 4 and 4 x 1024 x 4 floats (the ITN's 128^2
-// layers: 512 planes at B = 8): 0 = 256 x 16 float4 (2 blocks, 8 waves per CU), 1 = 1024 x
-// 4, 2 = 512 x 8, 3 = the pipelined kernels on two planes per 512-thread block (A/B:
-// STX_IN128; B8 x 64 @ 128^2 ReLU, same box: fwd / bwd 13.9 / 18.9, 13.7 / 21.7, 13.5 /
-// 18.0, 14.6 / 19.0 us -- none pays, 0 is kept)
-static int in128_form() {
-  static const int v = STX_KNOB("STX_IN128", 0);
-  return v;
-}
-
-static int in_ppb() {  // planes per block of the pipelined 64^2 kernels (1: one-plane kernels)
-  // 1, 2 or 4 (the launches below instantiate these; anything else means 1)
-  static const int v = [] {
-    const int k = STX_KNOB("STX_IN_PPB", 4);
-    return k == 2 || k == 4 ? k : 1;
-  }();
-  return v;
-}
-
-// Large planes (the ITN's 256^2 layers: 64 K floats, 1024 threads x 16 float4): g stays
-// in registers (64 VGPRs) and u = x (+ res) is kept too -- its first XL float4s per thread
-// in registers, the rest in LDS (XL = 8: 32 VGPRs + 128 KB of LDS, one block per CU) -- so
-// the plane is read once: dy and u in, du out (the round-5 form re-read u in its second
-// pass: 4 plane-reads + 1 write instead of 2 + 1).  The ReLU decision is recomputed from u.
+// Large planes (the ITN's 256^2 layers: 64 K floats, 512 threads x 32 float4) under a
+// ReLU and without a residual: g stays in registers and u = x is kept too -- its first
+// GREG_XL float4s per thread in registers, the rest in LDS (one block per CU) -- so the
+// plane is read once: dy and u in, du out.  The ReLU decision is recomputed from u.
 // Same arithmetic as instnorm_bwd_reg_kernel.
-template <int NT, int R4, bool RELU, bool RES, int XL>
-__global__ void __launch_bounds__(NT)
+constexpr int GREG_NT = 512, GREG_R4 = 32, GREG_XL = 14;
+
+__global__ void __launch_bounds__(GREG_NT)
 instnorm_bwd_greg_kernel(const float* __restrict__ dy, const float* __restrict__ beta,
                          const float* __restrict__ x, const float* __restrict__ res,
                          const float* __restrict__ gamma, const float* __restrict__ mean,
                          const float* __restrict__ rstd, float* __restrict__ du,
                          float* __restrict__ parts, int c, int hw, int relu,
                          float* __restrict__ out_amax) {
+  constexpr int NT = GREG_NT, R4 = GREG_R4, XL = GREG_XL;
   __shared__ float red[NT / 64];
-  // u of steps XL .. R4-1 ([step][thread]); XL < 0: u not kept, re-read in the second pass
-  __shared__ f32x4 ul[XL < 0 ? 1 : (R4 - XL) * NT];
+  __shared__ f32x4 ul[(R4 - XL) * NT];  // u of steps XL .. R4-1 ([step][thread])
   const size_t base = (size_t)blockIdx.x * hw;
   const int ch = blockIdx.x % c;
   const float mu = mean[blockIdx.x], rs = rstd[blockIdx.x];
@@ -610,33 +595,29 @@ instnorm_bwd_greg_kernel(const float* __restrict__ dy, const float* __restrict__
   const uint32_t pbytes = (uint32_t)hw * 4u;
   const auto rdy = make_srd(dy + base, pbytes);
   const auto rx = make_srd(x + base, pbytes);
-  const auto rr = make_srd(RES ? res + base : x + base, pbytes);
   const auto rdu = make_srd(du + base, pbytes);
   const uint32_t lo = threadIdx.x * 16u;
   constexpr uint32_t KSTEP = NT * 16u;
   const int n4 = hw >> 2;
-  f32x4 g[R4], ur[XL > 0 ? XL : 1];
+  f32x4 g[R4], ur[XL];
   float sg = 0.f, sgx = 0.f;
 #pragma unroll
   for (int k = 0; k < R4; ++k) {
     const f32x4 d4 = __builtin_bit_cast(
         f32x4, __builtin_amdgcn_raw_buffer_load_b128(rdy, lo, k * KSTEP, 0));
-    f32x4 u4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, lo, k * KSTEP, 0));
-    if (RES) u4 += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, lo, k * KSTEP, 0));
+    const f32x4 u4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, lo, k * KSTEP, 0));
     const bool in = (int)threadIdx.x + k * NT < n4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      g[k][e] = (RELU && !(__builtin_fmaf(u4[e], gsc, sh) > 0.f)) ? 0.f : d4[e];
+      g[k][e] = !(__builtin_fmaf(u4[e], gsc, sh) > 0.f) ? 0.f : d4[e];
       const float xh = in ? (u4[e] - mu) * rs : 0.f;
       sg += g[k][e];
       sgx += g[k][e] * xh;
     }
-    if constexpr (XL >= 0) {
-      if (k < XL)
-        ur[k < XL ? k : 0] = u4;
-      else
-        ul[(k - XL) * NT + threadIdx.x] = u4;
-    }
+    if (k < XL)
+      ur[k < XL ? k : 0] = u4;
+    else
+      ul[(k - XL) * NT + threadIdx.x] = u4;
     // at most 2 steps of loads in flight (g and u take 96 VGPRs; the scheduler would
     // hoist more loads and spill)
     if ((k & 1) == 1) __builtin_amdgcn_sched_barrier(0);
@@ -649,14 +630,7 @@ instnorm_bwd_greg_kernel(const float* __restrict__ dy, const float* __restrict__
   float sdu = 0.f;
 #pragma unroll
   for (int k = 0; k < R4; ++k) {
-    f32x4 u4;
-    if constexpr (XL < 0) {
-      if ((k & 3) == 0) __builtin_amdgcn_sched_barrier(0);
-      u4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, lo, k * KSTEP, 0));
-      if (RES) u4 += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, lo, k * KSTEP, 0));
-    } else {
-      u4 = k < XL ? ur[k < XL ? k : 0] : ul[(k - XL) * NT + threadIdx.x];
-    }
+    const f32x4 u4 = k < XL ? ur[k < XL ? k : 0] : ul[(k - XL) * NT + threadIdx.x];
     const bool in = (int)threadIdx.x + k * NT < n4;
     f32x4 o;
 #pragma unroll
@@ -764,45 +738,19 @@ extern "C" int stx_instnorm_fwd(const float* x, const float* res, const float* g
     return STX_E_INVALID;
   }
   hipStream_t st = (hipStream_t)stream;
-  // 64^2 planes: 512 threads x 2 float4 per thread (fast_st 1801 -> 1811 img/s same box
-  // against 256 x 4; 128 x 8 was 0.6 % slower); STX_IN_CFG=0 restores 256 x 4, 1 = 128 x 8
-  static const int cfg = STX_KNOB("STX_IN_CFG", 2);
-#ifdef STX_AB  // 128 x 8 blocks for the 64^2 planes (measured 0.6 % slower)
-  if (cfg == 1 && hw % 4 == 0 && hw <= 4 * 128 * 8)
-    hipLaunchKernelGGL((instnorm_fwd_reg_kernel<128, 8>), dim3(n * c), dim3(128), 0, st, x, res,
-                       gamma, beta, y, mean, rstd, c, hw, eps, relu, out_amax);
-  else
-#endif
-  if (cfg == 2 && hw == 4 * 512 * 2 && in_ppb() > 1 && (n * c) % in_ppb() == 0 &&
-           n * c / in_ppb() >= 256 &&  // enough blocks to fill the chip (B = 8: 256)
-           ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(res) |
-             reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
-    const int ppb = in_ppb();
-    const dim3 grid(n * c / ppb);
-#define STX_IN_FWD_PIPE(P, R)                                                                   \
-  hipLaunchKernelGGL((instnorm_fwd_pipe_kernel<512, 2, P, R>), grid, dim3(512), 0, st, x, res, \
-                     gamma, beta, y, mean, rstd, c, eps, relu, out_amax)
-    if (ppb == 4) {
-      if (res) STX_IN_FWD_PIPE(4, true); else STX_IN_FWD_PIPE(4, false);
-    } else {
-      if (res) STX_IN_FWD_PIPE(2, true); else STX_IN_FWD_PIPE(2, false);
-    }
-#undef STX_IN_FWD_PIPE
-  } else if (cfg == 2 && hw % 4 == 0 && hw <= 4 * 512 * 2)
+  // 64^2 planes: 512 threads x 2 float4 per thread, four planes per block where that
+  // still fills the chip (B = 8: 256 blocks)
+  if (hw == PIPE_HW && (n * c) % PIPE_PPB == 0 && n * c / PIPE_PPB >= 256) {
+    const dim3 grid(n * c / PIPE_PPB);
+    if (res)
+      hipLaunchKernelGGL(instnorm_fwd_pipe_kernel<true>, grid, dim3(PIPE_NT), 0, st, x, res,
+                         gamma, beta, y, mean, rstd, c, eps, relu, out_amax);
+    else
+      hipLaunchKernelGGL(instnorm_fwd_pipe_kernel<false>, grid, dim3(PIPE_NT), 0, st, x, res,
+                         gamma, beta, y, mean, rstd, c, eps, relu, out_amax);
+  } else if (hw % 4 == 0 && hw <= 4 * 512 * 2)
     hipLaunchKernelGGL((instnorm_fwd_reg_kernel<512, 2>), dim3(n * c), dim3(512), 0, st, x, res,
                        gamma, beta, y, mean, rstd, c, hw, eps, relu, out_amax);
-  else if (hw % 4 == 0 && hw <= 4 * 256 * 4)
-    hipLaunchKernelGGL((instnorm_fwd_reg_kernel<256, 4>), dim3(n * c), dim3(256), 0, st, x, res,
-                       gamma, beta, y, mean, rstd, c, hw, eps, relu, out_amax);
-  else if (in128_form() == 3 && hw == 4 * 512 * 8 && !res && (n * c) % 2 == 0 && n * c / 2 >= 256)
-    hipLaunchKernelGGL((instnorm_fwd_pipe_kernel<512, 8, 2, false>), dim3(n * c / 2), dim3(512), 0,
-                       st, x, res, gamma, beta, y, mean, rstd, c, eps, relu, out_amax);
-  else if (in128_form() == 1 && hw % 4 == 0 && hw <= 4 * 1024 * 4)
-    hipLaunchKernelGGL((instnorm_fwd_reg_kernel<1024, 4>), dim3(n * c), dim3(1024), 0, st, x,
-                       res, gamma, beta, y, mean, rstd, c, hw, eps, relu, out_amax);
-  else if (in128_form() == 2 && hw % 4 == 0 && hw <= 4 * 512 * 8)
-    hipLaunchKernelGGL((instnorm_fwd_reg_kernel<512, 8>), dim3(n * c), dim3(512), 0, st, x,
-                       res, gamma, beta, y, mean, rstd, c, hw, eps, relu, out_amax);
   else if (hw % 4 == 0 && hw <= 4 * 256 * 16)
     hipLaunchKernelGGL((instnorm_fwd_reg_kernel<256, 16>), dim3(n * c), dim3(256), 0, st, x, res,
                        gamma, beta, y, mean, rstd, c, hw, eps, relu, out_amax);
@@ -842,68 +790,24 @@ extern "C" int stx_instnorm_bwd(const float* dy, const float* beta, const float*
   const bool al = ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x) |
                     reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(du)) & 15) == 0 &&
                   hw % 4 == 0;
-  // block shape of the 64^2 kernels, as stx_instnorm_fwd
-  static const int cfg = STX_KNOB("STX_IN_CFG", 2);
-#ifdef STX_AB
-  if (cfg == 1 && al && hw <= 4 * 128 * 8)
-    hipLaunchKernelGGL((instnorm_bwd_reg_kernel<128, 8>), dim3(n * c), dim3(128), 0, st, dy, beta, x,
-                       res, gamma, mean, rstd, du, (float*)ws, c, hw, relu, out_amax);
-  else
-#endif
-  if (cfg == 2 && al && hw == 4 * 512 * 2 && in_ppb() > 1 && (n * c) % in_ppb() == 0 &&
-           n * c / in_ppb() >= 256) {
-    const int ppb = in_ppb();
-    const dim3 grid(n * c / ppb);
-#define STX_IN_BWD_PIPE(P, RL, R)                                                               \
-  hipLaunchKernelGGL((instnorm_bwd_pipe_kernel<512, 2, P, RL, R>), grid, dim3(512), 0, st, dy, beta, \
-                     x, res, gamma, mean, rstd, du, (float*)ws, c, out_amax)
-    if (ppb == 4) {
-      if (relu) { if (res) STX_IN_BWD_PIPE(4, true, true); else STX_IN_BWD_PIPE(4, true, false); }
-      else { if (res) STX_IN_BWD_PIPE(4, false, true); else STX_IN_BWD_PIPE(4, false, false); }
-    } else {
-      if (relu) { if (res) STX_IN_BWD_PIPE(2, true, true); else STX_IN_BWD_PIPE(2, true, false); }
-      else { if (res) STX_IN_BWD_PIPE(2, false, true); else STX_IN_BWD_PIPE(2, false, false); }
-    }
+  // 64^2 planes: block shapes as stx_instnorm_fwd
+  if (al && hw == PIPE_HW && (n * c) % PIPE_PPB == 0 && n * c / PIPE_PPB >= 256) {
+    const dim3 grid(n * c / PIPE_PPB);
+#define STX_IN_BWD_PIPE(RL, R)                                                                 \
+  hipLaunchKernelGGL((instnorm_bwd_pipe_kernel<RL, R>), grid, dim3(PIPE_NT), 0, st, dy, beta, x, \
+                     res, gamma, mean, rstd, du, (float*)ws, c, out_amax)
+    if (relu) { if (res) STX_IN_BWD_PIPE(true, true); else STX_IN_BWD_PIPE(true, false); }
+    else { if (res) STX_IN_BWD_PIPE(false, true); else STX_IN_BWD_PIPE(false, false); }
 #undef STX_IN_BWD_PIPE
-  } else if (cfg == 2 && al && hw <= 4 * 512 * 2)
+  } else if (al && hw <= 4 * 512 * 2)
     hipLaunchKernelGGL((instnorm_bwd_reg_kernel<512, 2>), dim3(n * c), dim3(512), 0, st, dy, beta, x,
                        res, gamma, mean, rstd, du, (float*)ws, c, hw, relu, out_amax);
-  else if (al && hw <= 4 * 256 * 4)
-    hipLaunchKernelGGL((instnorm_bwd_reg_kernel<256, 4>), dim3(n * c), dim3(256), 0, st, dy, beta, x,
-                       res, gamma, mean, rstd, du, (float*)ws, c, hw, relu, out_amax);
-  else if (in128_form() == 3 && al && hw == 4 * 512 * 8 && relu && !res && (n * c) % 2 == 0 &&
-           n * c / 2 >= 256)
-    hipLaunchKernelGGL((instnorm_bwd_pipe_kernel<512, 8, 2, true, false>), dim3(n * c / 2),
-                       dim3(512), 0, st, dy, beta, x, res, gamma, mean, rstd, du, (float*)ws, c,
-                       out_amax);
-  else if (in128_form() == 1 && al && hw <= 4 * 1024 * 4)
-    hipLaunchKernelGGL((instnorm_bwd_reg_kernel<1024, 4>), dim3(n * c), dim3(1024), 0, st, dy,
-                       beta, x, res, gamma, mean, rstd, du, (float*)ws, c, hw, relu, out_amax);
-  else if (in128_form() == 2 && al && hw <= 4 * 512 * 8)
-    hipLaunchKernelGGL((instnorm_bwd_reg_kernel<512, 8>), dim3(n * c), dim3(512), 0, st, dy,
-                       beta, x, res, gamma, mean, rstd, du, (float*)ws, c, hw, relu, out_amax);
   else if (al && hw <= 4 * 256 * 16)
     hipLaunchKernelGGL((instnorm_bwd_reg_kernel<256, 16>), dim3(n * c), dim3(256), 0, st, dy, beta,
                        x, res, gamma, mean, rstd, du, (float*)ws, c, hw, relu, out_amax);
-  else if (al && hw <= 4 * 1024 * 16 && relu && !res && greg_on())  // 256^2 IN + ReLU
-  {
-    // u kept in registers + LDS at 512 threads per plane (STX_GREG_FORM A/B, B8 x 32 planes
-    // of 256^2, same box: 0 = u re-read in the second pass at 1024 threads 51.0 us, 1 = u
-    // kept at 1024 threads 44.1 us (spills 24 VGPRs), 2 = this 40.1 us)
-    static const int form = STX_KNOB("STX_GREG_FORM", 2);
-    if (form == 0)
-      hipLaunchKernelGGL((instnorm_bwd_greg_kernel<1024, 16, true, false, -1>), dim3(n * c),
-                         dim3(1024), 0, st, dy, beta, x, res, gamma, mean, rstd, du, (float*)ws,
-                         c, hw, relu, out_amax);
-    else if (form == 2)
-      hipLaunchKernelGGL((instnorm_bwd_greg_kernel<512, 32, true, false, 14>), dim3(n * c),
-                         dim3(512), 0, st, dy, beta, x, res, gamma, mean, rstd, du, (float*)ws,
-                         c, hw, relu, out_amax);
-    else
-      hipLaunchKernelGGL((instnorm_bwd_greg_kernel<1024, 16, true, false, 7>), dim3(n * c),
-                         dim3(1024), 0, st, dy, beta, x, res, gamma, mean, rstd, du, (float*)ws,
-                         c, hw, relu, out_amax);
-  }
+  else if (al && hw <= 4 * GREG_NT * GREG_R4 && relu && !res && greg_on())  // 256^2 IN + ReLU
+    hipLaunchKernelGGL(instnorm_bwd_greg_kernel, dim3(n * c), dim3(GREG_NT), 0, st, dy, beta, x,
+                       res, gamma, mean, rstd, du, (float*)ws, c, hw, relu, out_amax);
   else if (hw >= 4 * 1024 * 4)  // big planes (256^2): 16 waves per plane
     hipLaunchKernelGGL(instnorm_bwd_kernel<1024>, dim3(n * c), dim3(1024), 0, st, dy, beta, x, res,
                        gamma, mean, rstd, du, (float*)ws, c, hw, relu, out_amax);

@@ -43,7 +43,7 @@ struct Wg16 {
   int ncot, ncit, nsplit, steps, steps_per_split;
   int cout32, cin32;
   int ci2;  // cout <= 32: a wave takes 32 couts x 64 cins (two cin tiles), not 64 x 32
-  int lds;  // wgrad16_lds_kernel geometry (cout 64/128, 64-cin tiles, 1 block per CU; 2: K2)
+  int lds;  // wgrad16_lds_kernel geometry (cout 128, 64-cin tiles, 1 block per CU; 2: K2)
 };
 
 // Blocks are dealt round-robin over the 8 XCDs (b and b + 8 share one L2): renumber
@@ -56,7 +56,7 @@ __device__ __forceinline__ int xcd_block(int b, int nb) {
 
 constexpr int WG16_S2 = 16;  // private mode: stride 2, pad 1, raw input (h = 2 hv, w = 2 wv)
 
-template <int PF, bool S2, bool CI2 = false>
+template <bool S2, bool CI2 = false>
 __global__ void __launch_bounds__(256)
 wgrad16_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ ws,
                const float* __restrict__ x_amax, const float* __restrict__ dy_amax, Wg16 g) {
@@ -324,7 +324,7 @@ wgrad16_kernel(const float* __restrict__ x, const float* __restrict__ dy, float*
     }
   };
 
-  // four steps of loads in flight (HBM latency >> one step of 9 MFMAs)
+  constexpr int PF = 4;  // steps of loads in flight (HBM latency >> one step of 9 MFMAs)
   const int s0 = split * g.steps_per_split;
   const int s1 = min(g.steps, s0 + g.steps_per_split);
   {
@@ -677,8 +677,8 @@ wgrad16up_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, Wg
   }
 }
 
-// LDS-staged variant for the ITN's stride-1 layers with cout in {64, 128} and
-// cin % 64 == 0 (the residual convs 128 -> 128, the up convs 128 -> 64): a block
+// LDS-staged variant for the ITN's stride-1 layers with cout = 128 and
+// cin % 64 == 0 (the residual convs 128 -> 128): a block
 // owns (all couts, 64 cins, kh) over a K split and steps through 16-pixel rows.
 // The V row segment (64 cins x 18 pixels incl. the kw halo) is split ONCE per block
 // into fp16 hi/lo and written to LDS as the three kw-shifted copies the B fragments
@@ -688,24 +688,25 @@ wgrad16up_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, Wg
 // global loads in flight.  Against wgrad16_kernel this removes the 4x redundant
 // V conversion of its four waves and halves the number of K splits (1 block per CU
 // instead of 8 waves), so the split-K slab the reduce kernel reads is half as big.
-// CIB = cins per block (64; 128 for cout = 64, so each wave still owns two 32 x 32
-// (co, ci) tiles: 18 MFMAs per barrier instead of 9)
+// UP: nearest x2 upsampled input
 // RL: ReLU input (compile time: no per-element select)
 // K2: two groups of four waves per block (512 threads) take alternate 16-pixel steps of the
 // block's K range, each with its own double-buffered V images and accumulators, so two waves
 // per SIMD share the MFMA pipe (the 4-wave block has one: its staging, barrier and operand
 // latency leave the pipe idle); group 1's sums are added to group 0's through LDS at the
 // end (fixed order), the partial slab and the split count stay those of the 4-wave block.
-template <int WCO, bool UP, int PF, int CIB = 64, bool RL = false, bool K2 = false>
-__global__ void __launch_bounds__(K2 ? 512 : 256, 1)  // WCO = couts / 32; UP: nearest x2
-wgrad16_lds_kernel(const float* __restrict__ x, const float* __restrict__ dy,  // upsampled
-                   float* __restrict__ ws, const float* __restrict__ x_amax,   // input; PF + 1
-                   const float* __restrict__ dy_amax, Wg16 g) {               // steps in flight
+template <bool UP, bool RL = false, bool K2 = false>
+__global__ void __launch_bounds__(K2 ? 512 : 256, 1)
+wgrad16_lds_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                   float* __restrict__ ws, const float* __restrict__ x_amax,
+                   const float* __restrict__ dy_amax, Wg16 g) {
+  constexpr int PF = 3;                    // load ring: PF + 1 steps in flight
+  constexpr int CIB = 64;                  // cins per block
   constexpr int NCI = CIB / 64;            // staged cin rows per thread
-  constexpr int NPAIR = WCO * 2 * NCI / 4;  // (co tile, ci tile) pairs per wave
+  constexpr int NPAIR = 2 * NCI;           // (co tile, ci tile) pairs per wave (128 couts, 4 waves)
   constexpr int NG = K2 ? 2 : 1;           // step groups
   static_assert((PF + 1) % 2 == 0, "ring slot k stages into V image k & 1");
-  constexpr int IMG = 3 * 2 * 2 * CIB * 16;  // one V image: 12|24 KB
+  constexpr int IMG = 3 * 2 * 2 * CIB * 16;  // one V image: 12 KB
   constexpr int RED = K2 ? 4 * NPAIR * 3 * 16 * 64 * 4 : 0;  // group 1's accumulators
   constexpr int LDSB = 2 * NG * IMG > RED ? 2 * NG * IMG : RED;
   __shared__ __attribute__((aligned(16))) char smem[LDSB];
@@ -723,9 +724,8 @@ wgrad16_lds_kernel(const float* __restrict__ x, const float* __restrict__ dy,  /
   const float descale = __builtin_ldexpf(1.f, ex + ed - 30);
   const int H = g.hv, W = g.wv, wsteps = W / 16;
   constexpr bool relu = RL;
-  // this wave's (co tile, ci tile) pairs: WCO = 4 -> co tile = wave, ci tiles 0, 1;
-  // WCO = 2 -> co tile = wave & 1, ci tile(s) (wave >> 1) * NCI + 0 .. NCI - 1
-  const int cot = WCO == 4 ? wave : (wave & 1);
+  // this wave's (co tile, ci tile) pairs: co tile = wave, every ci tile of the block
+  const int cot = wave;
   const int co = cot * 32 + l32;
   // V staging: thread -> (ci = tid / 4, quad q = tid % 4): pixels x0 + 4q - 1 .. x0 + 4q + 4
   const int sci = tid >> 2, q = tid & 3;
@@ -840,8 +840,7 @@ wgrad16_lds_kernel(const float* __restrict__ x, const float* __restrict__ dy,  /
     }
 #pragma unroll
     for (int pi = 0; pi < NPAIR; ++pi) {
-      // ci tile (32 cins) within the block's CIB
-      const int ct = WCO == 4 ? pi : (wave >> 1) * NCI + (NPAIR > 1 ? pi : 0);
+      const int ct = pi;  // ci tile (32 cins) within the block's CIB
 #pragma unroll
       for (int kw = 0; kw < 3; ++kw) {
         const h8 bh = *reinterpret_cast<const h8*>(img + (((kw * 2 + 0) * 2 + h) * CIB + ct * 32 + l32) * 16);
@@ -905,7 +904,7 @@ wgrad16_lds_kernel(const float* __restrict__ x, const float* __restrict__ dy,  /
   // partial [split][kh*3+kw][co (cout32)][ci (cin32)], descaled (exact)
 #pragma unroll
   for (int pi = 0; pi < NPAIR; ++pi) {
-    const int ct = WCO == 4 ? pi : (wave >> 1) * NCI + (NPAIR > 1 ? pi : 0);
+    const int ct = pi;
 #pragma unroll
     for (int kw = 0; kw < 3; ++kw) {
       float* out = ws + (((size_t)split * 9 + kh * 3 + kw) * g.cout32 + cot * 32) * g.cin32 +
@@ -924,55 +923,22 @@ static bool wg16_lds_on() {
   return on;
 }
 
-// cout 64 on the LDS kernel (STX_WG16_LDS64=1): 64 cins per block measured 1.6x slower
-// than the register-direct kernel, 128 cins per block (cin % 128 == 0) 5 % slower on the
-// ITN up conv (188 vs 179 us, same box): off by default
-static bool lds_on_64() {
-  static const bool on = STX_KNOB("STX_WG16_LDS64", 0) != 0;
-  return on;
-}
-
 typedef void (*Wg16Kernel)(const float*, const float*, float*, const float*, const float*, Wg16);
-
-constexpr int WG16_K2_PF = 3;  // the K2 blocks' load ring
 
 static int wg16_threads(const Wg16& g) { return g.lds == 2 ? 512 : 256; }
 
-static int wg16_pf() {
-  static const int pf = STX_KNOB("STX_WG16_PF", 4);
-  return pf;
-}
-
 // the kernel a planned geometry launches (g.lds / g.ci2 / mode / cout / cin set)
 static Wg16Kernel wg16_kernel(const Wg16& g) {
+  if (g.lds == 2)  // (K2: not upsampled -- wg16_plan)
+    return g.mode == STX_IN_RELU ? wgrad16_lds_kernel<false, true, true>
+                                 : wgrad16_lds_kernel<false, false, true>;
   if (g.lds) {
-    const bool up = g.mode == STX_IN_UPSAMPLE2;
-#ifdef STX_AB  // measured variants (not in the product build): load-ring depths, cout 64
-    if (g.mode == STX_IN_RELU && g.cout != 128)
-      return wgrad16_lds_kernel<2, false, 3, 64, true>;
-    static const int lpf = STX_KNOB("STX_WG16_LPF", 3);
-    if (g.cout == 128 && !up && lpf >= 5)
-      return lpf >= 7 ? wgrad16_lds_kernel<4, false, 7> : wgrad16_lds_kernel<4, false, 5>;
-    if (g.cout != 128) {
-      if (g.cin % 128 == 0)
-        return up ? wgrad16_lds_kernel<2, true, 3, 128> : wgrad16_lds_kernel<2, false, 3, 128>;
-      return up ? wgrad16_lds_kernel<2, true, 3> : wgrad16_lds_kernel<2, false, 3>;
-    }
-#endif
-    if (g.lds == 2)  // (K2: cout 128, not upsampled -- wg16_plan)
-      return g.mode == STX_IN_RELU ? wgrad16_lds_kernel<4, false, WG16_K2_PF, 64, true, true>
-                                   : wgrad16_lds_kernel<4, false, WG16_K2_PF, 64, false, true>;
-    if (g.mode == STX_IN_RELU) return wgrad16_lds_kernel<4, false, 3, 64, true>;
-    return up ? wgrad16_lds_kernel<4, true, 3> : wgrad16_lds_kernel<4, false, 3>;
+    if (g.mode == STX_IN_RELU) return wgrad16_lds_kernel<false, true>;
+    return g.mode == STX_IN_UPSAMPLE2 ? wgrad16_lds_kernel<true> : wgrad16_lds_kernel<false>;
   }
   if (g.mode == WG16_UPP) return g.ci2 ? wgrad16up_kernel<2, true> : wgrad16up_kernel<2, false>;
-  if (g.ci2) return wgrad16_kernel<4, false, true>;
-  if (g.mode == WG16_S2) return wgrad16_kernel<4, true>;
-#ifdef STX_AB
-  const int pf = wg16_pf();
-  if (pf >= 8) return pf >= 12 ? wgrad16_kernel<12, false> : wgrad16_kernel<8, false>;
-#endif
-  return wgrad16_kernel<4, false>;
+  if (g.ci2) return wgrad16_kernel<false, true>;
+  return g.mode == WG16_S2 ? wgrad16_kernel<true> : wgrad16_kernel<false>;
 }
 
 // resident blocks of `k` over the whole device (CUs x blocks per CU at `threads`);
@@ -1030,11 +996,11 @@ static bool wg16_plan(int n, int cin, int cout, int in_mode, int hv, int wv, Wg1
     g.cin32 = g.ncit * 32;
   }
   g.steps = n * hv * (wv / 16);
-  g.lds = wg16_lds_on() && (cout == 128 || (cout == 64 && lds_on_64())) && cin % 64 == 0 &&
+  g.lds = wg16_lds_on() && cout == 128 && cin % 64 == 0 &&
           (in_mode == STX_IN_RAW || in_mode == STX_IN_RELU || in_mode == STX_IN_UPSAMPLE2);
   // (read per plan: A/B in one process; both forms run one block per CU, so the split
   // count and the workspace are the same)
-  if (g.lds && cout == 128 && in_mode != STX_IN_UPSAMPLE2 && STX_KNOB("STX_WG16_K2", 1)) g.lds = 2;
+  if (g.lds && in_mode != STX_IN_UPSAMPLE2 && STX_KNOB("STX_WG16_K2", 1)) g.lds = 2;
   // the upsampled input as parity classes (4 instead of 9 MACs per output; STX_WG16_UPP=0:
   // the upsampled-row kernels): 32-column steps over the output rows of one row parity
   static const bool upp_on = STX_KNOB("STX_WG16_UPP", 1) != 0;
@@ -1044,7 +1010,7 @@ static bool wg16_plan(int n, int cin, int cout, int in_mode, int hv, int wv, Wg1
   }
   if (g.lds) {  // blocks of (all couts x 64 cins x kh) x K split: ~512 blocks
     g.ncot = 1;
-    g.ncit = cout == 64 && cin % 128 == 0 ? cin / 128 : cin / 64;  // CIB
+    g.ncit = cin / 64;
     g.cout32 = cout;
     g.cin32 = cin;
     g.ci2 = 0;

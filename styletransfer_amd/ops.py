@@ -11,8 +11,6 @@ import contextlib
 import ctypes as C
 import gc
 
-import os
-
 import torch
 
 from . import _native as N
@@ -96,7 +94,6 @@ class SideStream:
         self.keep = []
 
     def begin(self, device):
-        import os
         if N.knob("STX_WGRAD_SIDE", "0") != "1":
             return
         key = torch.device(device).index or 0
@@ -631,7 +628,6 @@ def conv2d_wgrad(x, dy, cin, cout, ks, stride=1, pad=None, in_mode=N.STX_IN_RAW,
     if dw is None:
         dw = torch.empty((cout, cin, ks, ks), device=x.device, dtype=torch.float32)
     L = lib()
-    import os
     split = split and N.knob("STX_CONV_SPLIT", "1") != "0"
     if split and ks == 9 and stride == 1 and pad == 4 and in_mode == N.STX_IN_RAW:
         # ITN conv0 / conv22: the 3-channel side expanded per tap row (wgrad9.hip)

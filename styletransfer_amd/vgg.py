@@ -253,23 +253,6 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
     st.alpha = alpha
     st.c4 = c4
     split = N.knob("STX_GRAM_SPLIT", "1") != "0"
-    overlap = N.knob("STX_LOSS_STREAM", "0") != "0"  # measured slower (A/B)
-    main = torch.cuda.current_stream(dev)
-    side = _side_stream(dev) if overlap else main
-    capturing = False
-    if overlap:
-        # the side stream never grows the shared scratch buffer: size it here, on main
-        L = N.lib()
-        hw = [(64, H * W), (64, H * W), (128, (H // 2) * (W // 2)),
-              (128, (H // 2) * (W // 2)), (256, (H // 4) * (W // 4))]
-        need = max([L.stx_gram_ws(B, c, n) for c, n in hw] +
-                   [L.stx_mse_ws(B * 128 * (H // 2) * (W // 2))])
-        ops.WS.get(need, dev)
-        side.wait_stream(main)
-        capturing = torch.cuda.is_current_stream_capturing()
-        if not capturing:
-            for t in [st.losses, st.amax, c4] + [c for c in st.coef if c is not None]:
-                t.record_stream(side)
 
     # conv layers whose Gram partials come out of the conv epilogue (no re-read of Z)
     hs = [H, H, H // 2, H // 2, H // 4]
@@ -297,8 +280,6 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
         content = (c4, st.mse_parts)
     # the five taps' Gram finalizes in one launch after the forward (STX_FIN_BATCH=0: one
     # finalize launch per tap, right after its partials)
-    # (with the loss stream the jobs are recorded on the side stream's calls and the one
-    # finalize launch runs on main after the join)
     fin = ops.FinalizeBatch() if N.knob("STX_FIN_BATCH", "1") != "0" else None
 
     def tap_loss(i, l, z, b_, c_, fuse_mse):
@@ -331,39 +312,24 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
     st.coef_amax = [None] * 5  # (per style tap)
 
     def on_layer(l, z):
-        # the style loss of layer l (and the content/feature losses at conv2_2) run on
-        # the side stream while the next conv runs: memory-bound reductions under
-        # compute-bound convs, joined before the backward
-        if overlap:
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
-            if not capturing:
-                z.record_stream(side)
-        with torch.cuda.stream(side):
-            i = STYLE_CONVS.index(l)
-            b_, c_ = z.shape[:2]
-            fuse_mse = l == CONTENT_CONV and st.grams[l] is None and split and fuse_content
-            L = N.lib()
-            need = (L.stx_style_content_ws if fuse_mse else L.stx_gram_ws)(b_, c_,
-                                                                             z[0, 0].numel())
-            if st.lws[i] is None or st.lws[i].numel() < need:
-                st.lws[i] = torch.empty(need, device=dev, dtype=torch.uint8)
-            njobs = len(fin.jobs) if fin is not None else 0
-            tap_loss(i, l, z, b_, c_, fuse_mse)
-            if i in COEF_AMAX_SLOT and fin is not None and len(fin.jobs) == njobs + 1:
-                # the batched finalize also writes max|A| of the taps whose Gram backward
-                # runs inside a data-gradient conv: that phase's split-MFMA A scale
-                st.coef_amax[i] = slot(st.amax, COEF_AMAX_SLOT[i])
-                fin.jobs[-1].coef_amax = st.coef_amax[i].data_ptr()
+        # the style loss of layer l (and the content/feature losses at conv2_2)
+        i = STYLE_CONVS.index(l)
+        b_, c_ = z.shape[:2]
+        fuse_mse = l == CONTENT_CONV and st.grams[l] is None and split and fuse_content
+        L = N.lib()
+        need = (L.stx_style_content_ws if fuse_mse else L.stx_gram_ws)(b_, c_, z[0, 0].numel())
+        if st.lws[i] is None or st.lws[i].numel() < need:
+            st.lws[i] = torch.empty(need, device=dev, dtype=torch.uint8)
+        njobs = len(fin.jobs) if fin is not None else 0
+        tap_loss(i, l, z, b_, c_, fuse_mse)
+        if i in COEF_AMAX_SLOT and fin is not None and len(fin.jobs) == njobs + 1:
+            # the batched finalize also writes max|A| of the taps whose Gram backward
+            # runs inside a data-gradient conv: that phase's split-MFMA A scale
+            st.coef_amax[i] = slot(st.amax, COEF_AMAX_SLOT[i])
+            fin.jobs[-1].coef_amax = st.coef_amax[i].data_ptr()
 
     st.z = feat.forward(x, 5, st.z if st.z else None, amax=st.amax, pools=st.pools,
                         on_layer=on_layer, grams=st.grams, content=content)
-    if overlap:
-        main.wait_stream(side)
-        if not capturing:
-            for c in st.coef:
-                c.record_stream(main)
     if fin is not None:
         # (the jobs stay on the state for bench.py's per-tap cost of the batched launch)
         st.fin_jobs = list(fin.jobs)
@@ -382,9 +348,6 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
     return st
 
 
-_SIDE = {}
-
-
 # amax groups of LossState.amax: 0..5 forward, 6..10 backward split-conv inputs, 11 / 12
 # max|A| of the taps whose Gram backward is a data-gradient conv's second phase
 LOSS_AMAX_GROUPS = 17  # LossState.amax: the groups below
@@ -396,15 +359,6 @@ COMPOSE_AMAX_SLOT = 13  # max|A5 W| of the composed conv3_1 data-gradient weight
 def slot(amax, k):
     """The k-th amax group of a slot vector (include/stx.h STX_AMAX_SLOTS)."""
     return amax[k * N.STX_AMAX_SLOTS:(k + 1) * N.STX_AMAX_SLOTS]
-
-
-def _side_stream(dev):
-    """Per-device secondary stream for the loss reductions (loss_forward)."""
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    s = _SIDE.get(key)
-    if s is None:
-        s = _SIDE[key] = torch.cuda.Stream(torch.device("cuda", key))
-    return s
 
 
 def loss_values(st: LossState):

@@ -1,6 +1,5 @@
 """Conv + fused 128-channel Gram (conv_gram_tile128) at the Gatys / fast_st conv2_x
-shapes: the plain conv (64-cout blocks), the same conv on 8-wave 128-cout blocks
-(STX_FORCE_WM2=1, measurement build only), with the fused Gram, and with the Gram plus
+shapes: the plain conv (64-cout blocks), with the fused Gram, and with the Gram plus
 the content MSE sums; beside the standalone Gram kernels it replaces.  HIP events on the
 launch stream."""
 import os

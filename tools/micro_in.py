@@ -1,6 +1,7 @@
 """InstanceNorm backward of the ITN's 256^2 ReLU layers (B = 8, 32 channels: the
-instnorm_bwd_greg kernel) by HIP events; prints the time and a checksum of du so the
-STX_GREG_FORM variants of the measurement library can be compared (same bits expected)."""
+instnorm_bwd_greg kernel) by HIP events; prints the time and a checksum of du so that
+STX_IN_GREG=0/1 of the measurement library can be compared (same bits expected);
+`micro_in.py 128`: the 128^2 layers, forward and backward."""
 import os
 import sys
 
