@@ -178,7 +178,7 @@ const char* stx_last_error_string(void);
 /* The ABI revision of this header (STX_ABI_VERSION): a host binding refuses a library of
  * another revision rather than pass arguments whose meaning changed (round 6:
  * stx_instnorm_bwd's second argument is beta, not y; 7: stx_conv_params.unpool_out). */
-#define STX_ABI_VERSION 7
+#define STX_ABI_VERSION 8
 int stx_abi_version(void);
 
 /* Padded GEMM dims the conv kernels expect for a (cin, cout, ks) conv. */
@@ -544,6 +544,41 @@ int stx_instnorm_bwd(const float* dy, const float* beta, const float* x, const f
                      float* dgamma, float* dbeta, float* dbias_in, int n, int c, int hw, int relu,
                      int accumulate_params, float* out_amax, void* ws, size_t ws_bytes,
                      void* stream);
+
+/* Conditional instance norm (Dumoulin et al., "A Learned Representation for Artistic
+ * Style"): N styles share one network; only the IN affine rows are per style, tables
+ * gtab / btab [S][c] per layer.  The IN kernels above index their affine vectors by
+ * plane % c only, so a per-sample affine [n][c] is stx_instnorm_fwd/bwd called with
+ * (n = 1, c = n*c) -- same kernel selection, speed and bits.  Two launches per step
+ * serve every IN layer (one job each); mix [n][S] holds each sample's style weights
+ * (a one-hot row selects a style, a convex row blends).
+ *   stx_cin_mix:  gamma_n[k][ch] = sum_s mix[k][s] gtab[s][ch] (beta_n from btab), an
+ *     fma chain from 0 with s ascending: a one-hot row reproduces the table row's bits.
+ *     Needs gtab, btab, gamma_n, beta_n.
+ *   stx_cin_param_grads:  from the layer's stx_instnorm_bwd partials `parts` [n*c][3]
+ *     (that call ran with (1, n*c) and dgamma = dbeta = dbias_in = NULL into its own
+ *     workspace),  dgtab[s][ch] (+)= sum_k mix[k][s] parts[k][ch][0],  dbtab likewise
+ *     from [1],  dbias_in[ch] (+)= sum_k parts[k][ch][2];  k ascending, the order of
+ *     stx_instnorm_param_grads (all samples on one style: that row has its sums' bits,
+ *     the other rows get 0).  Needs parts; dgtab, dbtab, dbias_in may be NULL. */
+#define STX_CIN_MAX 32
+typedef struct stx_cin_job {
+  const float* gtab;
+  const float* btab; /* [S][c] style tables */
+  float* gamma_n;
+  float* beta_n;      /* mix: out [n][c] */
+  const float* parts; /* grads: the layer's stx_instnorm_bwd partials [n*c][3] */
+  float* dgtab;
+  float* dbtab;    /* grads: [S][c], any may be NULL */
+  float* dbias_in; /* grads: [c] (producing conv's bias), may be NULL */
+  int c, accumulate;
+} stx_cin_job;
+int stx_cin_mix(const stx_cin_job* jobs, int njobs, const float* mix, int n, int S,
+                void* stream);
+int stx_cin_param_grads(const stx_cin_job* jobs, int njobs, const float* mix, int n, int S,
+                        void* stream);
+/* sizeof and last-member offset of stx_cin_job, as stx_abi_layout gives the older structs' */
+int stx_cin_abi_layout(long long* out, int n);
 
 /* nearest x2 upsample: y [nc][2h][2w];  backward dx[y][x] = sum of dy's 2x2 block */
 int stx_upsample2x_fwd(const float* x, float* y, int nc, int h, int w, void* stream);

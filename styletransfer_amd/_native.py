@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("STX_LIB", os.path.join(_HERE, "libstx.so"))
 STX_IN_RAW, STX_IN_RELU, STX_IN_RELU_POOL2, STX_IN_UPSAMPLE2, STX_IN_DILATE2 = range(5)
 STX_AMAX_SLOTS = 32  # an "amax" is a group of 32 floats whose max is the value (stx.h)
 STX_GRAM_GROUP = 8  # fused Gram partials per in-kernel group sum (stx_conv_params.gram_cnt)
-STX_ABI_VERSION = 7  # include/stx.h: the library must report the same revision
+STX_ABI_VERSION = 8 # include/stx.h: the library must report the same revision
 
 
 def knob(name: str, default: str) -> str:
@@ -77,6 +77,15 @@ class PGradJob(C.Structure):
 
 
 STX_PGRAD_MAX = 32
+
+
+class CinJob(C.Structure):
+    """Mirror of `stx_cin_job` (include/stx.h)."""
+    _fields_ = [("gtab", vp), ("btab", vp), ("gamma_n", vp), ("beta_n", vp), ("parts", vp),
+                ("dgtab", vp), ("dbtab", vp), ("dbias_in", vp), ("c", i32), ("accumulate", i32)]
+
+
+STX_CIN_MAX = 32
 
 
 class LossParts(C.Structure):
@@ -179,6 +188,9 @@ SIGNATURES = {
     "stx_instnorm_param_grads": (i32, [C.POINTER(PGradJob), i32, vp]),
     "stx_instnorm_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32,
                                i32, i32, vp, vp, sz, vp]),
+    "stx_cin_mix": (i32, [C.POINTER(CinJob), i32, vp, i32, i32, vp]),
+    "stx_cin_param_grads": (i32, [C.POINTER(CinJob), i32, vp, i32, i32, vp]),
+    "stx_cin_abi_layout": (i32, [vp, i32]),
     "stx_upsample2x_fwd": (i32, [vp, vp, i32, i32, i32, vp]),
     "stx_upsample2x_bwd": (i32, [vp, vp, i32, i32, i32, vp]),
     "stx_tv_ws": (sz, [i32, i32, i32, i32]),

@@ -298,6 +298,64 @@ def instance_norm(x, gamma, beta, res=None, eps=1e-5, relu=False, conv_bias=None
     return InstanceNormFn.apply(x, res, gamma, beta, eps, relu, conv_bias, res_link)
 
 
+class CondInstanceNormFn(torch.autograd.Function):
+    """InstanceNormFn with a per-sample affine (conditional instance norm): gamma_n /
+    beta_n [n][c] are the step's mix of the style tables gtab / btab [S][c] (ops.cin_mix,
+    one launch for the whole net), and the tables' gradients come from the backward's
+    per-plane partials through ops.CINGRADS.  Same fusions (res, relu, conv_bias,
+    res_link) and amax handling; the ReLU mask is recomputed from the same gamma_n /
+    beta_n bits."""
+
+    @staticmethod
+    def forward(ctx, x, res, gtab, btab, gamma_n, beta_n, mix, eps, relu, conv_bias=None,
+                res_link=None):
+        x, res = _c(x), _c(res)
+        g = ops.ARENA.take(x.device)
+        y, mean, rstd = ops.instnorm_fwd(x, gamma_n, beta_n, res=res, eps=eps, relu=relu,
+                                         out_amax=g, per_sample=True)
+        ops.ARENA.annotate(y, g)
+        ctx.save_for_backward(x, res, gamma_n, beta_n, mix, mean, rstd)
+        ctx.tabs = (gtab, btab)
+        ctx.cb_ref = conv_bias
+        ctx.relu = relu
+        ctx.has_res = res is not None
+        ctx.res_link = res_link if res is not None else None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, res, gamma_n, beta_n, mix, mean, rstd = ctx.saved_tensors
+        c = x.shape[1]
+        gtab, btab = ctx.tabs
+        cb = ctx.cb_ref if ctx.needs_input_grad[9] else None
+        params = (gtab if ctx.needs_input_grad[2] else None,
+                  btab if ctx.needs_input_grad[3] else None, cb)
+        # straight into existing .grad buffers (the trainer's flat gradient)
+        acc = all(p is None or (p.is_leaf and p.grad is not None and p.grad.is_contiguous())
+                  for p in params)
+        bufs = [None if p is None else (p.grad if acc else torch.empty(p.shape, device=x.device))
+                for p in params]
+        ga = ops.ARENA.take(x.device)
+        du = ops.instnorm_bwd(_c(dy), beta_n, x, res, gamma_n, mean, rstd, relu=ctx.relu,
+                              dgamma=bufs[0], dbeta=bufs[1], dbias_in=bufs[2], accumulate=acc,
+                              out_amax=ga, per_sample=True, mix=mix)
+        ops.ARENA.annotate(du, ga)
+        dg, db, dcb = (None, None, None) if acc else bufs
+        dres = None
+        if ctx.has_res:
+            if ctx.res_link is not None and ctx.res_link.accepted and ctx.needs_input_grad[1]:
+                ctx.res_link.g = du  # added by the block's first conv (ResLink)
+            else:
+                dres = du
+        return du, dres, dg, db, None, None, None, None, None, dcb, None
+
+
+def cond_instance_norm(x, gtab, btab, gamma_n, beta_n, mix, res=None, eps=1e-5, relu=False,
+                       conv_bias=None, res_link=None):
+    return CondInstanceNormFn.apply(x, res, gtab, btab, gamma_n, beta_n, mix, eps, relu,
+                                    conv_bias, res_link)
+
+
 # ----------------------------------------------------------------------- losses
 class GramFn(torch.autograd.Function):
     """StyleLoss.gram_matrix: G = F Fᵀ / (C·H·W) (stransfer/network.py:92-108)."""

@@ -41,6 +41,57 @@ def train(style_image_path, epochs, batch_size, content_weight, style_weight, sy
 
 
 @fast_st.command()
+@click.argument("style-image-paths", nargs=-1, required=True)
+@click.option("-n", "--name", required=True, help="Name of the multi-style network")
+@click.option("-e", "--epochs", default=50, help="How many epochs the training will take")
+@click.option("-b", "--batch-size", default=4, help="Batch size for training")
+@click.option("-cw", "--content-weight", default=1,
+              help="The weight we will assign to the content loss during the optimization")
+@click.option("-sw", "--style-weight", default=100_000,
+              help="The weight we will assign to the style loss during the optimization")
+@click.option("--synthetic", default=0, type=int,
+              help="Train on N synthetic images instead of local COCO (no network here)")
+def train_multi(style_image_paths, name, epochs, batch_size, content_weight, style_weight,
+                synthetic):
+    """Train ONE network on several styles (conditional instance norm): checkpoints
+    data/models/fast_mst_NAME_epoch*.pth and the style names in fast_mst_NAME.styles.json."""
+    from .. import distributed
+    distributed.from_env()
+    names = [p.split("/")[-1] for p in style_image_paths]
+    if len(set(names)) != len(names):
+        raise click.UsageError(f"style image names must differ: {names}")
+    LOGGER.info("Training multi-style network %s on styles: %s", name, names)
+    styles = [img_utils.image_loader(os.path.join(constants.PROJECT_ROOT_PATH, p))
+              for p in style_image_paths]
+    net = network.MultiStyleTransformNet(styles, batch_size, style_names=names)
+    loaders = ((lambda shard: dataset.get_synthetic_loader(batch_size, n_train=synthetic,
+                                                            shard=shard))
+               if synthetic else None)
+    net.static_train(style_name=name, epochs=epochs, style_weight=style_weight,
+                     content_weight=content_weight, loaders=loaders)
+
+
+@fast_st.command()
+@click.argument("image-path")
+@click.argument("name")
+@click.option("--mix", default=None,
+              help='Style weights "a.jpg:0.3,b.jpg:0.7" (normalised to sum 1); default: the '
+                   "first style")
+@click.option("-o", "--out-dir", default="results/",
+              help="The results directory where the converted image will be saved")
+def convert_image_multi(image_path, name, mix, out_dir):
+    """Convert IMAGE-PATH with the multi-style network NAME, blending its styles by --mix."""
+    try:
+        names = network.MultiStyleTransformNet.load_style_names(name)
+        weights = network.parse_mix(mix, names)
+    except (OSError, ValueError) as e:
+        raise click.UsageError(str(e))
+    sty = network.MultiStyleTransformNet([torch.rand([3, 8, 8])] * len(names),
+                                         style_names=names)
+    sty.process_image(image_path=image_path, name=name, mix=weights, out_dir=out_dir)
+
+
+@fast_st.command()
 @click.argument("image-path")
 @click.argument("style-name")
 @click.option("-o", "--out-dir", default="results/",

@@ -47,3 +47,12 @@ extern "C" int stx_abi_layout(long long* out, int n) {
   for (int i = 0; out && i < n && i < m; ++i) out[i] = v[i];
   return m;
 }
+
+// the same for stx_cin_job, which came after that table's count was pinned
+extern "C" int stx_cin_abi_layout(long long* out, int n) {
+  const long long v[] = {(long long)sizeof(stx_cin_job),
+                         (long long)offsetof(stx_cin_job, accumulate)};
+  const int m = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; out && i < n && i < m; ++i) out[i] = v[i];
+  return m;
+}

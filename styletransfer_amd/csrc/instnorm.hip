@@ -698,9 +698,131 @@ __global__ void __launch_bounds__(256) instnorm_param_grads_kernel(PGradJobs b) 
   if (t.dbias_in) t.dbias_in[ch] = acc ? t.dbias_in[ch] + d : d;
 }
 
+// conditional instance norm (N styles per network): the per-sample affine rows of every
+// IN layer in one launch, and the style tables' gradients of every layer in one launch
+struct CinJobs {
+  stx_cin_job job[STX_CIN_MAX];
+  int ch0[STX_CIN_MAX + 1];  // first channel of each job (prefix sums)
+  int njobs;
+};
+
+__device__ __forceinline__ int cin_find_job(const CinJobs& b, int gc) {
+  int j = 0;
+  while (j + 1 < b.njobs && gc >= b.ch0[j + 1]) ++j;
+  return j;
+}
+
+// thread -> (sample, job, channel): gamma_n[k][ch] = sum_s mix[k][s] gtab[s][ch] as an fma
+// chain from 0, s ascending (a one-hot row gives the table row's bits)
+__global__ void __launch_bounds__(256) cin_mix_kernel(CinJobs b, const float* __restrict__ mix,
+                                                      int n, int S) {
+  const int ctot = b.ch0[b.njobs];
+  const int gi = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gi >= n * ctot) return;
+  const int k = gi / ctot, gc = gi - k * ctot;
+  const int j = cin_find_job(b, gc);
+  const stx_cin_job& t = b.job[j];
+  const int ch = gc - b.ch0[j];
+  const float* m = mix + (size_t)k * S;
+  float g = 0.f, be = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const float w = m[s];
+    g = __builtin_fmaf(w, t.gtab[(size_t)s * t.c + ch], g);
+    be = __builtin_fmaf(w, t.btab[(size_t)s * t.c + ch], be);
+  }
+  t.gamma_n[(size_t)k * t.c + ch] = g;
+  t.beta_n[(size_t)k * t.c + ch] = be;
+}
+
+// thread -> (style, job, channel): dgtab[s][ch] (+)= sum_k mix[k][s] parts[k][ch][0] (dbtab:
+// [1]), and the style-0 threads dbias_in[ch] (+)= sum_k parts[k][ch][2]; k ascending, the
+// order of instnorm_param_grads_kernel (fma(1, p, a) == a + p: one style gives its sums' bits)
+__global__ void __launch_bounds__(256) cin_param_grads_kernel(CinJobs b,
+                                                              const float* __restrict__ mix,
+                                                              int n, int S) {
+  const int ctot = b.ch0[b.njobs];
+  const int gi = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gi >= S * ctot) return;
+  const int s = gi / ctot, gc = gi - s * ctot;
+  const int j = cin_find_job(b, gc);
+  const stx_cin_job& t = b.job[j];
+  const int ch = gc - b.ch0[j];
+  const bool acc = t.accumulate != 0;
+  const float* p0 = t.parts + 3 * (size_t)ch;
+  const size_t pk = 3 * (size_t)t.c;  // partials of the next sample
+  if (t.dgtab || t.dbtab) {
+    float a = 0.f, bb = 0.f;
+    for (int k = 0; k < n; ++k) {
+      const float w = mix[(size_t)k * S + s];
+      a = __builtin_fmaf(w, p0[k * pk], a);
+      bb = __builtin_fmaf(w, p0[k * pk + 1], bb);
+    }
+    const size_t o = (size_t)s * t.c + ch;
+    if (t.dgtab) t.dgtab[o] = acc ? t.dgtab[o] + a : a;
+    if (t.dbtab) t.dbtab[o] = acc ? t.dbtab[o] + bb : bb;
+  }
+  if (s == 0 && t.dbias_in) {
+    float d = 0.f;
+    for (int k = 0; k < n; ++k) d += p0[k * pk + 2];
+    t.dbias_in[ch] = acc ? t.dbias_in[ch] + d : d;
+  }
+}
+
 }  // namespace stx
 
 using namespace stx;
+
+// the argument checks both conditional-IN entry points share; fills the kernel's job table
+static int cin_pack(const char* what, const stx_cin_job* jobs, int njobs, const float* mix, int n,
+                    int S, bool grads, CinJobs& b) {
+  if (!jobs || njobs <= 0 || njobs > STX_CIN_MAX) {
+    set_error("%s: 1 <= njobs <= %d required", what, STX_CIN_MAX);
+    return STX_E_INVALID;
+  }
+  if (!mix || n <= 0 || S <= 0) {
+    set_error("%s: mix, n > 0 and S > 0 required", what);
+    return STX_E_INVALID;
+  }
+  long long ch = 0;
+  for (int j = 0; j < njobs; ++j) {
+    const stx_cin_job& t = jobs[j];
+    const bool ptrs = grads ? t.parts != nullptr
+                            : (t.gtab && t.btab && t.gamma_n && t.beta_n);
+    if (t.c <= 0 || !ptrs) {
+      set_error("%s: job %d invalid (c > 0 and %s required)", what, j,
+                grads ? "parts" : "gtab, btab, gamma_n, beta_n");
+      return STX_E_INVALID;
+    }
+    b.job[j] = t;
+    b.ch0[j] = (int)ch;
+    ch += t.c;
+    if (ch * (grads ? S : n) > 0x7fffff00LL) {  // (one thread each, an int index)
+      set_error("%s: too many channels", what);
+      return STX_E_INVALID;
+    }
+  }
+  b.ch0[njobs] = (int)ch;
+  b.njobs = njobs;
+  return STX_OK;
+}
+
+extern "C" int stx_cin_mix(const stx_cin_job* jobs, int njobs, const float* mix, int n, int S,
+                           void* stream) {
+  CinJobs b{};
+  if (int rc = cin_pack("stx_cin_mix", jobs, njobs, mix, n, S, false, b)) return rc;
+  hipLaunchKernelGGL(cin_mix_kernel, dim3(cdiv(n * b.ch0[njobs], 256)), dim3(256), 0,
+                     (hipStream_t)stream, b, mix, n, S);
+  return check_launch("stx_cin_mix");
+}
+
+extern "C" int stx_cin_param_grads(const stx_cin_job* jobs, int njobs, const float* mix, int n,
+                                   int S, void* stream) {
+  CinJobs b{};
+  if (int rc = cin_pack("stx_cin_param_grads", jobs, njobs, mix, n, S, true, b)) return rc;
+  hipLaunchKernelGGL(cin_param_grads_kernel, dim3(cdiv(S * b.ch0[njobs], 256)), dim3(256), 0,
+                     (hipStream_t)stream, b, mix, n, S);
+  return check_launch("stx_cin_param_grads");
+}
 
 extern "C" int stx_instnorm_param_grads(const stx_in_pgrad_job* jobs, int njobs, void* stream) {
   if (!jobs || njobs <= 0 || njobs > STX_PGRAD_MAX) {

@@ -91,6 +91,50 @@ class InstanceNorm2d(nn.InstanceNorm2d):
                                conv_bias=conv_bias, res_link=res_link)
 
 
+class CinState:
+    """The current per-sample style weights of a multi-style net, shared by all of its
+    ConditionalInstanceNorm2d layers: `mix` [n][S] (fp32, on the device) and, per layer,
+    the affine rows [n][c] mixed from its tables -- network.MultiStyleTransformNet fills
+    `rows` for every layer with one launch at the start of its forward; a layer without
+    an entry (used on its own) mixes its rows itself."""
+
+    def __init__(self):
+        self.mix = None
+        self.rows = {}
+
+    def set(self, mix, rows=None):
+        self.mix = mix
+        self.rows = {} if rows is None else rows
+
+
+class ConditionalInstanceNorm2d(InstanceNorm2d):
+    """Conditional instance norm (Dumoulin et al., "A Learned Representation for Artistic
+    Style"): `weight` / `bias` are style tables [S][C]; sample k is normalised with the
+    rows `state.mix[k] @ table` (a one-hot row selects a style, a convex row blends)."""
+
+    def __init__(self, num_styles, num_features, eps=1e-5, state=None):
+        super().__init__(num_features, eps=eps, affine=True)
+        if num_styles < 1:
+            raise ValueError("num_styles >= 1 required")
+        self.num_styles = int(num_styles)
+        self.weight = nn.Parameter(torch.ones(self.num_styles, num_features))
+        self.bias = nn.Parameter(torch.zeros(self.num_styles, num_features))
+        self.state = state if state is not None else CinState()
+
+    def forward(self, x, relu=False, res=None, conv_bias=None, res_link=None):
+        from . import ops
+        mix = self.state.mix
+        if mix is None or mix.shape[0] != x.shape[0]:
+            raise ValueError(f"ConditionalInstanceNorm2d: state.mix must be [{x.shape[0]}]"
+                             f"[{self.num_styles}] (set by the net's forward or CinState.set)")
+        rows = self.state.rows.get(self)
+        if rows is None:
+            rows = ops.cin_mix([(self.weight.detach(), self.bias.detach())], mix)[0]
+        return A.cond_instance_norm(x, self.weight, self.bias, rows[0], rows[1], mix, res=res,
+                                    eps=self.eps, relu=relu, conv_bias=conv_bias,
+                                    res_link=res_link)
+
+
 class Upsample(nn.Upsample):
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)

@@ -378,15 +378,18 @@ class StyleNetwork(nn.Module):
 class ResidualBlock(nn.Module):
     """stransfer/network.py:461-506: conv-IN-ReLU-conv, + x, IN (no final ReLU)."""
 
-    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1):
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, norm=None):
         super().__init__()
+        # norm: channels -> normalisation layer (an InstanceNorm2d subclass); None: the
+        # reference's InstanceNorm2d(affine=True)
+        norm = norm if norm is not None else (lambda c: InstanceNorm2d(c, affine=True))
         self.conv1 = Conv2d(in_channels, out_channels, kernel_size, stride, kernel_size // 2,
                             padding_mode="reflection")
-        self.insn1 = InstanceNorm2d(out_channels, affine=True)
+        self.insn1 = norm(out_channels)
         self.relu = ReLU()
         self.conv2 = Conv2d(out_channels, out_channels, kernel_size, stride, kernel_size // 2,
                             padding_mode="reflection")
-        self.insn2 = InstanceNorm2d(out_channels, affine=True)
+        self.insn2 = norm(out_channels)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         # IN + ReLU fused; (+ residual) + IN fused; each conv's bias gradient comes out of
@@ -399,22 +402,23 @@ class ResidualBlock(nn.Module):
                           res_link=link)
 
 
-def _itn_layers(in_channels=3):
+def _itn_layers(in_channels=3, norm=None):
+    norm = norm if norm is not None else (lambda c: InstanceNorm2d(c, affine=True))
+
     def conv(i, o, k, s, up=False):
         c = Conv2d(i, o, kernel_size=k, stride=s, padding=k // 2, padding_mode="reflection")
         c._up_input = up  # behind an Upsample (forward fuses it into the conv)
         return c
 
     return [
-        conv(in_channels, 32, 9, 1), InstanceNorm2d(32, affine=True), ReLU(),
-        conv(32, 64, 3, 2), InstanceNorm2d(64, affine=True), ReLU(),
-        conv(64, 128, 3, 2), InstanceNorm2d(128, affine=True), ReLU(),
-        ResidualBlock(128, 128, 3), ResidualBlock(128, 128, 3), ResidualBlock(128, 128, 3),
-        ResidualBlock(128, 128, 3), ResidualBlock(128, 128, 3),
+        conv(in_channels, 32, 9, 1), norm(32), ReLU(),
+        conv(32, 64, 3, 2), norm(64), ReLU(),
+        conv(64, 128, 3, 2), norm(128), ReLU(),
+        *(ResidualBlock(128, 128, 3, norm=norm) for _ in range(5)),
         Upsample(mode="nearest", scale_factor=2),
-        conv(128, 64, 3, 1, up=True), InstanceNorm2d(64, affine=True), ReLU(),
+        conv(128, 64, 3, 1, up=True), norm(64), ReLU(),
         Upsample(mode="nearest", scale_factor=2),
-        conv(64, 32, 3, 1, up=True), InstanceNorm2d(32, affine=True), ReLU(),
+        conv(64, 32, 3, 1, up=True), norm(32), ReLU(),
         conv(32, 3, 9, 1),
     ]
 
@@ -425,8 +429,10 @@ class ImageTransformNet(nn.Sequential):
     Upsample->Conv (upsampling inside the conv's halo load), Conv->IN->ReLU and the
     residual add."""
 
-    def __init__(self, style_image: torch.Tensor, batch_size=4, in_channels=3):
-        super().__init__(*_itn_layers(in_channels))
+    model_name = "fast_st"  # checkpoint prefix in data/models/
+
+    def __init__(self, style_image: torch.Tensor, batch_size=4, in_channels=3, norm=None):
+        super().__init__(*_itn_layers(in_channels, norm))
         assert isinstance(style_image, torch.Tensor), "Style image need to be already loaded"
         self.style_image = style_image
         self.batch_size = batch_size
@@ -471,6 +477,19 @@ class ImageTransformNet(nn.Sequential):
         return optimizer(self.parameters())
 
     # ---------------------------------------------------------------- workflows
+    def _make_trainer(self, dev, shard, style_weight, content_weight):
+        from .train import FastStTrainer
+        return FastStTrainer(self, self.style_image.to(dev), style_weight=style_weight,
+                             content_weight=content_weight, world_size=shard.world,
+                             process_group=shard.group)
+
+    def _test_network(self, trainer):
+        """What static_test evaluates with (its second argument)."""
+        return trainer.loss_network()
+
+    def _checkpoint_written(self, style_name):
+        """After a checkpoint of `style_name` is saved (rank 0)."""
+
     def static_train(self, style_name="nsp", epochs=50, style_weight=100_000, content_weight=1,
                      loaders=None, graph=True):
         """stransfer/network.py:651-770, data-parallel when launched with torchrun.
@@ -483,7 +502,6 @@ class ImageTransformNet(nn.Sequential):
         Shard and returning them) overrides COCO, e.g. dataset.get_synthetic_loader.
         graph=True replays each step as hipGraphs (FastStTrainer.train_step)."""
         from . import distributed as D
-        from .train import FastStTrainer
         shard = D.from_env()
         dev = D.device_for(shard)
         if next(self.parameters()).device != dev:
@@ -491,10 +509,8 @@ class ImageTransformNet(nn.Sequential):
         main = shard.is_main
         tb_writer = (get_tensorboard_writer(f"runs/fast-image-style-transfer-still-image_{style_name}")
                      if main else _NullWriter())
-        trainer = FastStTrainer(self, self.style_image.to(dev), style_weight=style_weight,
-                                content_weight=content_weight, world_size=shard.world,
-                                process_group=shard.group)
-        loss_network = trainer.loss_network() if main else None
+        trainer = self._make_trainer(dev, shard, style_weight, content_weight)
+        loss_network = self._test_network(trainer) if main else None
         if main:
             LOGGER.info('Training network with "%s" optimizer on %d data-parallel rank(s)',
                         type(trainer.opt), shard.world)
@@ -508,7 +524,7 @@ class ImageTransformNet(nn.Sequential):
         for epoch in range(epochs):
             if main:
                 LOGGER.info("Starting epoch %d", epoch)
-            ckpt = f"data/models/fast_st_{style_name}_epoch{epoch}.pth"
+            ckpt = f"data/models/{self.model_name}_{style_name}_epoch{epoch}.pth"
             if os.path.isfile(ckpt):
                 self.load_state_dict(adaptive_torch_load(ckpt))
                 trainer.resync_params()
@@ -537,6 +553,7 @@ class ImageTransformNet(nn.Sequential):
                 trainer.train_step(batch, graph=graph)
             if main:
                 torch.save(self.state_dict(), ckpt)
+                self._checkpoint_written(style_name)
             shard.barrier()
         return trainer
 
@@ -565,6 +582,162 @@ class ImageTransformNet(nn.Sequential):
         out_dir = os.path.join(constants.PROJECT_ROOT_PATH, out_dir)
         os.makedirs(out_dir, exist_ok=True)
         img_utils.imshow(out, path=os.path.join(out_dir, f"converted_fast_st_{style_name}.png"))
+
+
+def parse_mix(spec, names):
+    """'a.jpg:0.3,b.jpg:0.7' -> the weights of `names` (a network's styles in row order),
+    normalised to sum 1.  A style without ':w' counts 1; None / '' selects the first
+    style.  Unknown or repeated names, malformed or negative weights and a zero sum are
+    ValueErrors."""
+    names = list(names)
+    w = [0.0] * len(names)
+    if not spec:
+        w[0] = 1.0
+        return w
+    seen = set()
+    for item in spec.split(","):
+        name, sep, val = item.strip().rpartition(":")
+        if not sep:
+            name, val = val, "1"
+        if name not in names:
+            raise ValueError(f"unknown style {name!r}: this network holds {names}")
+        if name in seen:
+            raise ValueError(f"style {name!r} given twice")
+        seen.add(name)
+        try:
+            v = float(val)
+        except ValueError:
+            raise ValueError(f"style {name!r}: weight {val!r} is not a number") from None
+        if not (0.0 <= v < float("inf")):
+            raise ValueError(f"style {name!r}: weight {v} must be finite and >= 0")
+        w[names.index(name)] = v
+    total = sum(w)
+    if total <= 0.0:
+        raise ValueError("the mix weights sum to 0")
+    return [v / total for v in w]
+
+
+class MultiStyleTransformNet(ImageTransformNet):
+    """N styles in one ImageTransformNet by conditional instance normalisation (Dumoulin
+    et al., "A Learned Representation for Artistic Style"): every convolution is shared,
+    only the 15 InstanceNorm affine pairs are per style -- the same 62 state_dict keys
+    with the IN tensors [S][C].  `forward(x, style)` takes a style index, a LongTensor [B]
+    of indices, or mix weights [B][S] / [S] (a convex row blends styles); one launch mixes
+    every layer's per-sample rows, then the single-style kernels run unchanged."""
+
+    model_name = "fast_mst"
+
+    def __init__(self, style_images, batch_size=4, style_names=None):
+        from .layers import CinState, ConditionalInstanceNorm2d
+        if isinstance(style_images, torch.Tensor):
+            style_images = list(style_images) if style_images.dim() == 4 else [style_images]
+        style_images = list(style_images)
+        assert style_images and all(isinstance(s, torch.Tensor) for s in style_images), \
+            "Style images need to be already loaded"
+        S = len(style_images)
+        state = CinState()
+        super().__init__(style_images[0], batch_size,
+                         norm=lambda c: ConditionalInstanceNorm2d(S, c, state=state))
+        self.style_images = style_images
+        self.num_styles = S
+        self.style_names = list(style_names) if style_names is not None else \
+            [f"style{i}" for i in range(S)]
+        assert len(self.style_names) == S
+        self.cin = state
+        self._cin_layers = [m for m in self.modules() if isinstance(m, ConditionalInstanceNorm2d)]
+
+    def mix_of(self, style, n, device=None):
+        """`style` (None = style 0, int, LongTensor [n], float [S] or [n][S]) as the
+        kernels' mix [n][S] (fp32, on the device).  A float [n][S] device tensor is taken
+        as it is (the trainer's static buffer)."""
+        S = self.num_styles
+        device = device if device is not None else next(self.parameters()).device
+        if style is None:
+            style = 0
+        if isinstance(style, int):
+            if not 0 <= style < S:
+                raise ValueError(f"style {style}: this network holds {S}")
+            style = torch.full((n,), style, dtype=torch.long)
+        style = torch.as_tensor(style)
+        if not style.dtype.is_floating_point:
+            if style.shape != (n,):
+                raise ValueError(f"style ids {tuple(style.shape)}: [{n}] expected")
+            if int(style.min()) < 0 or int(style.max()) >= S:
+                raise ValueError(f"style ids must be in [0, {S})")
+            style = torch.nn.functional.one_hot(style.long(), S)
+        elif style.dim() == 1:
+            style = style.expand(n, -1)
+        if style.shape != (n, S):
+            raise ValueError(f"mix {tuple(style.shape)}: [{n}][{S}] or [{S}] expected")
+        return style.to(device, torch.float32).contiguous()
+
+    def forward(self, x: torch.Tensor, style=None) -> torch.Tensor:
+        from . import ops
+        x = x if x.is_cuda else _dev(x)
+        mix = self.mix_of(style, x.shape[0], x.device)
+        rows = ops.cin_mix([(m.weight.detach(), m.bias.detach()) for m in self._cin_layers], mix)
+        self.cin.set(mix, dict(zip(self._cin_layers, rows)))
+        return super().forward(x)
+
+    # ---------------------------------------------------------------- workflows
+    def _make_trainer(self, dev, shard, style_weight, content_weight):
+        from .train import MultiStyleTrainer
+        return MultiStyleTrainer(self, [s.to(dev) for s in self.style_images],
+                                 style_weight=style_weight, content_weight=content_weight,
+                                 world_size=shard.world, process_group=shard.group,
+                                 rank=shard.rank)
+
+    def _test_network(self, trainer):
+        return trainer
+
+    def _checkpoint_written(self, style_name):
+        import json
+        with open(f"data/models/{self.model_name}_{style_name}.styles.json", "w") as f:
+            json.dump(self.style_names, f)
+
+    def static_test(self, test_loader, trainer, style_weight=None, feature_weight=None):
+        """Average of the trainer's loss (train.MultiStyleTrainer.evaluate: sample j on
+        style j mod S) over the test batches."""
+        losses = [float(trainer.evaluate(_dev(b.squeeze(1)).contiguous())) for b in test_loader]
+        avg = torch.mean(torch.tensor(losses)) if losses else torch.tensor(float("nan"))
+        LOGGER.info("Average test loss: %.8f", float(avg))
+        return avg
+
+    @staticmethod
+    def load_style_names(name, models_path="data/models/"):
+        """The style names (table row order) written next to `name`'s checkpoints."""
+        import json
+        path = os.path.join(constants.PROJECT_ROOT_PATH, models_path,
+                            f"{MultiStyleTransformNet.model_name}_{name}.styles.json")
+        with open(path) as f:
+            names = json.load(f)
+        if not isinstance(names, list) or not all(isinstance(s, str) for s in names):
+            raise ValueError(f"{path}: a JSON list of style names expected")
+        return names
+
+    def load_latest(self, name, models_path="data/models/"):
+        """Load the lexicographically last `fast_mst_{name}_epoch*.pth`."""
+        root = os.path.join(constants.PROJECT_ROOT_PATH, models_path)
+        pre = f"{self.model_name}_{name}_epoch"
+        found = sorted(f for f in (os.listdir(root) if os.path.isdir(root) else [])
+                       if f.startswith(pre) and f.endswith(".pth"))
+        if not found:
+            raise AssertionError(f"There are no multi-style weights named {name!r} in {root}")
+        self.load_state_dict(adaptive_torch_load(os.path.join(root, found[-1])))
+
+    def process_image(self, image_path: str, name="nsp", mix=None, out_dir="results/"):
+        """Convert an image with the latest checkpoint of `name`; mix: None (the first
+        style), a style index, or weights [S] (parse_mix).  Returns the output tensor."""
+        self.load_latest(name)
+        image = img_utils.image_loader(os.path.join(constants.PROJECT_ROOT_PATH, image_path))
+        if mix is not None and not isinstance(mix, int):
+            mix = torch.as_tensor(mix, dtype=torch.float32)
+        with torch.no_grad():
+            out = self(image, style=mix)
+        out_dir = os.path.join(constants.PROJECT_ROOT_PATH, out_dir)
+        os.makedirs(out_dir, exist_ok=True)
+        img_utils.imshow(out, path=os.path.join(out_dir, f"converted_fast_mst_{name}.png"))
+        return out
 
 
 class VideoTransformNet(ImageTransformNet):

@@ -21,7 +21,7 @@ __all__ = [
     "conv2d", "conv_out_hw", "conv2d_wgrad",
     "bias_grad", "gram", "style_loss", "gram_bwd", "mse", "diff_scale", "loss_combine",
     "maxpool2x2", "maxpool2x2_bwd", "relupool_bwd", "relu", "relu_bwd", "adam_step",
-    "instnorm_fwd", "instnorm_bwd", "upsample2x", "upsample2x_bwd", "tv_loss",
+    "instnorm_fwd", "instnorm_bwd", "cin_mix", "upsample2x", "upsample2x_bwd", "tv_loss",
     "temporal_loss", "temporal_loss_bwd",
 ]
 
@@ -239,6 +239,48 @@ class ParamGradBatch:
 
 
 PGRADS = ParamGradBatch()
+
+
+class CinGradBatch:
+    """ParamGradBatch for conditional instance norm (stx_cin_param_grads): the style
+    tables' and conv biases' gradients of every per-sample IN layer of a step in one
+    launch.  Same life cycle: between begin() and flush() each instnorm_bwd(per_sample=
+    True) keeps its partials and records a job; outside a step add() reduces at once.
+    All jobs of a launch share the step's mix [n][S]."""
+
+    def __init__(self):
+        self.active = False
+        self.jobs, self.keep, self.mix = [], [], None
+
+    def begin(self):
+        self.active = True
+        self.jobs, self.keep, self.mix = [], [], None
+
+    def add(self, parts, mix, c, dgtab, dbtab, dbias, accumulate, defer=True):
+        if self.mix is not None and (self.mix.data_ptr() != mix.data_ptr() or
+                                     self.mix.shape != mix.shape):
+            self._launch()
+        self.mix = mix
+        self.keep.append(parts)
+        self.jobs.append(N.CinJob(None, None, None, None, parts.data_ptr(), _p(dgtab), _p(dbtab),
+                                  _p(dbias), c, int(accumulate)))
+        if len(self.jobs) == N.STX_CIN_MAX or not (self.active and defer):
+            self._launch()  # (with any jobs pending: their partials are written too)
+
+    def _launch(self):
+        if self.jobs:
+            arr = (N.CinJob * len(self.jobs))(*self.jobs)
+            n, S = self.mix.shape
+            check(lib().stx_cin_param_grads(arr, len(self.jobs), self.mix.data_ptr(), n, S,
+                                            _stream()), "stx_cin_param_grads")
+        self.jobs, self.keep, self.mix = [], [], None
+
+    def flush(self):
+        self._launch()
+        self.active = False
+
+
+CINGRADS = CinGradBatch()
 
 
 # ----------------------------------------------------------------------- conv
@@ -996,10 +1038,58 @@ def adam_step(p, g, m, v, step_dev, ws, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-
 
 
 # ----------------------------------------------------------------------- instance norm
-def instnorm_fwd(x, gamma, beta, res=None, eps=1e-5, relu=False, out=None, out_amax=None):
+def _mix_of(mix, n):
+    """A step's style weights as the kernels take them: fp32 [n][S] on the device."""
+    _req(mix, "mix")
+    if mix.dim() != 2 or mix.shape[0] != n:
+        raise ValueError(f"mix {tuple(mix.shape)}: [{n}][S] expected")
+    return mix
+
+
+def cin_mix(tables, mix):
+    """Per-sample affine rows of conditional instance norm layers in one launch
+    (stx_cin_mix).  tables: [(gtab, btab)] per layer, each [S][c]; mix [n][S].  Returns
+    [(gamma_n, beta_n)] per layer, each [n][c] = mix @ table (fma chain, s ascending: a
+    one-hot row reproduces the table row's bits)."""
+    tables = list(tables)
+    if not tables:
+        return []
+    n, S = _mix_of(mix, mix.shape[0]).shape
+    jobs, out = [], []
+    buf = torch.empty(2 * n * sum(g.shape[1] for g, _ in tables), device=mix.device,
+                      dtype=torch.float32)
+    o = 0
+    for g, b in tables:
+        _req(g, "gtab")
+        _req(b, "btab")
+        c = g.shape[1]
+        if tuple(g.shape) != (S, c) or tuple(b.shape) != (S, c):
+            raise ValueError(f"style tables {tuple(g.shape)} / {tuple(b.shape)}: [{S}][c] expected")
+        gn, bn = buf[o:o + n * c].view(n, c), buf[o + n * c:o + 2 * n * c].view(n, c)
+        o += 2 * n * c
+        out.append((gn, bn))
+        jobs.append(N.CinJob(g.data_ptr(), b.data_ptr(), gn.data_ptr(), bn.data_ptr(), None, None,
+                             None, None, c, 0))
+    for i in range(0, len(jobs), N.STX_CIN_MAX):
+        chunk = jobs[i:i + N.STX_CIN_MAX]
+        check(lib().stx_cin_mix((N.CinJob * len(chunk))(*chunk), len(chunk), mix.data_ptr(), n, S,
+                                _stream()), "stx_cin_mix")
+    return out
+
+
+def instnorm_fwd(x, gamma, beta, res=None, eps=1e-5, relu=False, out=None, out_amax=None,
+                 per_sample=False):
+    """per_sample: gamma / beta are [n][c] (a row per sample: conditional instance norm);
+    the kernels index their affine vectors by plane % c only, so the ABI is called with
+    (1, n*c) -- the same kernel selection and bits as the shared-affine call."""
     _req(x, "x")
     n, c = x.shape[:2]
     hw = x[0, 0].numel()
+    if per_sample:
+        for t in (gamma, beta):
+            if t is None or tuple(_req(t, "per-sample affine").shape) != (n, c):
+                raise ValueError(f"per_sample: gamma and beta must be [{n}][{c}]")
+        n, c = 1, n * c
     if out is None:
         out = torch.empty_like(x)
     mean = torch.empty(n * c, device=x.device, dtype=torch.float32)
@@ -1011,16 +1101,45 @@ def instnorm_fwd(x, gamma, beta, res=None, eps=1e-5, relu=False, out=None, out_a
 
 
 def instnorm_bwd(dy, beta, x, res, gamma, mean, rstd, relu=False, dgamma=None, dbeta=None,
-                 accumulate=False, out_amax=None, dbias_in=None):
+                 accumulate=False, out_amax=None, dbias_in=None, per_sample=False, mix=None):
     """du of y = [relu](IN(x (+res))*gamma + beta); dgamma / dbeta / dbias_in (the bias
     gradient of the conv that produced x, sum du) written or accumulated when given.
     beta: the forward's beta (None if it had none): with relu the kernel recomputes the
-    forward's y > 0 from x (+ res), mean, rstd, gamma, beta bit for bit (include/stx.h)."""
+    forward's y > 0 from x (+ res), mean, rstd, gamma, beta bit for bit (include/stx.h).
+    per_sample (conditional instance norm): gamma / beta are the forward's [n][c] rows and
+    the ABI is called with (1, n*c) as in instnorm_fwd; dgamma / dbeta are then the style
+    tables' gradients [S][c] and mix [n][S] the step's style weights -- they and dbias_in
+    come from the layer's partials through CINGRADS (one launch per step inside a
+    training step, else one here)."""
     n, c = x.shape[:2]
     hw = x[0, 0].numel()
     du = torch.empty_like(x)
     L = lib()
     need = L.stx_instnorm_bwd_ws(n, c)
+    if per_sample:
+        if gamma is None or tuple(gamma.shape) != (n, c) or beta is None or \
+                tuple(beta.shape) != (n, c):
+            raise ValueError(f"per_sample: gamma and beta must be [{n}][{c}]")
+        want = dgamma is not None or dbeta is not None or dbias_in is not None
+        if want:
+            S = _mix_of(mix, n).shape[1]
+            for t in (dgamma, dbeta):
+                if t is not None and tuple(_req(t, "table gradient").shape) != (S, c):
+                    raise ValueError(f"per_sample: table gradients must be [{S}][{c}]")
+            parts = torch.empty(need, device=x.device, dtype=torch.uint8)
+            wp, wn = parts.data_ptr(), need
+        else:
+            wp, wn = WS.get(need, x.device)
+        check(L.stx_instnorm_bwd(dy.data_ptr(), beta.data_ptr(), x.data_ptr(), _p(res),
+                                 gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                 du.data_ptr(), None, None, None, 1, n * c, hw, int(relu), 0,
+                                 _p(out_amax), wp, wn, _stream()), "stx_instnorm_bwd")
+        if want:
+            # deferred to the step's launch only when accumulating into persistent
+            # buffers; a fresh gradient tensor must be complete on return
+            CINGRADS.add(parts, mix, c, dgamma, dbeta, dbias_in, accumulate,
+                         defer=bool(accumulate))
+        return du
     # deferred only when accumulating into persistent buffers (.grad views): a fresh
     # gradient tensor handed back to autograd must be complete on return
     defer = PGRADS.active and accumulate and (

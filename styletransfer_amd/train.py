@@ -115,17 +115,24 @@ class FastStTrainer:
         self.slabs.prep()
         ops.ARENA.begin(self.device)  # InstanceNorm outputs carry their max|.| to the convs
         ops.PGRADS.begin()            # one launch for all InstanceNorm parameter gradients
+        ops.CINGRADS.begin()          # the same for conditional IN layers (launches nothing
+        #                               for a net without them)
         ops.SIDE.begin(self.device)   # weight gradients on a side stream
         try:
-            y = self.itn(batch)
+            y = self._forward(batch)
             total = self._total(batch, y)
             total.backward(self._one)
             ops.PGRADS.flush()
+            ops.CINGRADS.flush()
         finally:
             ops.SIDE.end()
             ops.PGRADS.active = False
+            ops.CINGRADS.active = False
             ops.ARENA.end()
         return total.detach()
+
+    def _forward(self, batch):
+        return self.itn(batch)
 
     def _exchange(self):
         # an explicit process group forces the exchange even at world 1 (the RCCL path
@@ -203,7 +210,119 @@ class FastStTrainer:
     @torch.no_grad()
     def evaluate(self, batch: torch.Tensor) -> torch.Tensor:
         batch = batch.to(self.device, torch.float32).contiguous()
-        return self._total(batch, self.itn(batch))
+        return self._total(batch, self._forward(batch))
+
+
+def style_ids(step, global_batch, n_styles, rank=0, world=1):
+    """The styles a multi-style training step trains on: global sample j of global step t
+    takes style (t*B + j) mod S -- every style equally often, whatever the batch size --
+    and rank r of `world` its contiguous slice of the B samples (the slice of the batch
+    distributed.ShardedBatchSampler gives it)."""
+    if global_batch % world:
+        raise ValueError(f"global batch {global_batch} does not divide over {world} ranks")
+    if not 0 <= rank < world or n_styles < 1:
+        raise ValueError("0 <= rank < world and n_styles >= 1 required")
+    b = global_batch // world
+    return [(step * global_batch + j) % n_styles for j in range(rank * b, (rank + 1) * b)]
+
+
+class MultiStyleTrainer(FastStTrainer):
+    """FastStTrainer for network.MultiStyleTransformNet: the step of the reference's
+    closure with sample k's style loss taken against the Grams of ITS style.  The style
+    Grams [S][C][C] per tap are computed once; per step the ids of the local samples
+    (style_ids, or given), their one-hot mix [b][S] and the gathered targets [b][C][C]
+    live in static buffers, so a captured step replays with whatever ids were copied in
+    before it: the target gathers, the net's row mix (stx_cin_mix) and the table-gradient
+    reduction (stx_cin_param_grads) are all inside the graph.  Data-parallel scaling and
+    the single flat all-reduce are FastStTrainer's."""
+
+    def __init__(self, itn, style_images, rank=0, **kw):
+        style_images = list(style_images)
+        super().__init__(itn, style_images[0], **kw)
+        self.S = len(style_images)
+        assert self.S == itn.num_styles, (self.S, itn.num_styles)
+        self.rank = int(rank)
+        per_style = []
+        for s in style_images:
+            s = s.to(self.device, torch.float32)
+            per_style.append(self.feat.style_targets(s.unsqueeze(0) if s.dim() == 3 else s))
+        # per tap [S][C][C]
+        self.style_grams = [torch.cat([t[i].reshape(1, *t[i].shape[-2:]) for t in per_style])
+                            .contiguous() for i in range(len(per_style[0]))]
+        self.style_images = style_images
+        self.t = 0          # steps taken (style_ids' step)
+        self._bufs = {}     # local batch size -> (ids, mix, gathered targets), all static
+        self._hold = False  # train_step has set this step's styles already
+        self._stage, self._slot = {}, 0  # pinned host staging of the ids and the mix
+
+    def _buffers(self, b):
+        if b not in self._bufs:
+            dev = self.device
+            self._bufs[b] = (torch.zeros(b, device=dev, dtype=torch.long),
+                             torch.zeros(b, self.S, device=dev, dtype=torch.float32),
+                             [torch.empty((b,) + tuple(T.shape[1:]), device=dev,
+                                          dtype=torch.float32) for T in self.style_grams])
+        return self._bufs[b]
+
+    def set_styles(self, b, ids=None, advance=True):
+        """This step's style ids of the b local samples into the static buffers (before a
+        replay: the captured graph reads them).  ids=None: style_ids of the step count."""
+        if ids is None:
+            ids = style_ids(self.t, b * self.world, self.S, self.rank, self.world)
+        ids = torch.as_tensor(ids, dtype=torch.long).reshape(-1)
+        if ids.numel() != b or int(ids.min()) < 0 or int(ids.max()) >= self.S:
+            raise ValueError(f"style ids: {b} values in [0, {self.S}) expected")
+        sid, mix, _ = self._buffers(b)
+        # through pinned staging (two slots, reused only after their copies ran): two async
+        # copies and no kernel, and the host does not wait for the previous step
+        self._slot ^= 1
+        key = (b, self._slot)
+        if key not in self._stage:
+            self._stage[key] = (torch.empty(b, dtype=torch.long).pin_memory(),
+                                torch.empty(b, self.S).pin_memory(), torch.cuda.Event())
+        hid, hmix, done = self._stage[key]
+        done.synchronize()  # (a never-recorded event returns at once)
+        hid.copy_(ids)
+        hmix.zero_()
+        hmix[torch.arange(b), ids] = 1.0
+        with torch.cuda.device(self.device):
+            sid.copy_(hid, non_blocking=True)
+            mix.copy_(hmix, non_blocking=True)
+            done.record()
+        if advance:
+            self.t += 1
+
+    def _forward(self, batch):
+        sid, mix, tg = self._buffers(batch.shape[0])
+        for T, t in zip(self.style_grams, tg):  # this step's targets: [b][C][C] per tap
+            torch.index_select(T, 0, sid, out=t)
+        self.targets = tg
+        return self.itn(batch, style=mix)
+
+    def step(self, batch, ids=None):
+        if not self._hold:
+            self.set_styles(batch.shape[0], ids)
+        return super().step(batch)
+
+    def train_step(self, batch, graph=True, ids=None):
+        self.set_styles(batch.shape[0], ids)
+        self._hold = True
+        try:
+            return super().train_step(batch, graph)
+        finally:
+            self._hold = False
+
+    @torch.no_grad()
+    def evaluate(self, batch, ids=None):
+        """The local loss of `batch` without a step; ids=None: style_ids of step 0."""
+        b = batch.shape[0]
+        self.set_styles(b, ids if ids is not None else
+                        style_ids(0, b * self.world, self.S, self.rank, self.world),
+                        advance=False)
+        return super().evaluate(batch)
+
+    def loss_network(self):
+        raise NotImplementedError("a multi-style net is tested through evaluate()")
 
 
 class VideoTrainer(FastStTrainer):
