@@ -177,8 +177,9 @@ int stx_abi_layout(long long* out, int n);
 const char* stx_last_error_string(void);
 /* The ABI revision of this header (STX_ABI_VERSION): a host binding refuses a library of
  * another revision rather than pass arguments whose meaning changed (round 6:
- * stx_instnorm_bwd's second argument is beta, not y; 7: stx_conv_params.unpool_out). */
-#define STX_ABI_VERSION 8
+ * stx_instnorm_bwd's second argument is beta, not y; 7: stx_conv_params.unpool_out;
+ * 9: the guided Gram entry points). */
+#define STX_ABI_VERSION 9
 int stx_abi_version(void);
 
 /* Padded GEMM dims the conv kernels expect for a (cin, cout, ks) conv. */
@@ -347,6 +348,34 @@ int stx_style_loss(const float* z, const float* target, float* g_out, float* coe
 int stx_gram_bwd(const float* coef, const float* z, float* dz, int b, int c, int h, int w,
                  const float* acc_scale_dev, const float* mask, const float* aux,
                  float aux_scale, int accumulate, void* stream);
+
+/* Guided (region-weighted) Gram -- the spatial control of Gatys et al. 2017, "Controlling
+ * Perceptual Factors in Neural Style Transfer".  R regions (1 <= R <= STX_GUIDE_MAX) with
+ * non-negative pixel weights wts [R][hw] shared over the batch (the host normalises each
+ * row to sum hw; w_max is a host float >= max wts):
+ *   G[b][r]  = 1/(c hw) sum_p wts[r][p] z[b][:,p] z[b][:,p]^T       g_out [b][R][c][c] or NULL
+ *   loss_r[r] = 1/(b c c) sum_{b,i,j} (G[b][r] - T[r])^2             target [R][c][c]
+ *   A[b][r]  = weight lambda[r] 4/(b c^3 hw) (G[b][r] - T[r])        coef [b][R][cpad][cpad]
+ * (cpad = stx_gram_coef_pitch(c); coef may be NULL; lambda: R host floats read at call
+ * time).  With z_amax (an amax group >= max|z|), hw % 8 == 0 and 16-byte aligned z / wts
+ * the partials run on the fp16 hi/lo split MFMA (A operand wts z at the power-of-two
+ * scale of w_max max|z|, B operand z), else on the fp32 MFMA; split-K partials summed in
+ * a fixed order.  R = 1 with all-ones weights is stx_style_loss's G, loss and A.
+ * ws >= stx_guided_style_ws(b, c, hw, R) (0: unsupported dims). */
+#define STX_GUIDE_MAX 4
+size_t stx_guided_style_ws(int b, int c, int hw, int R);
+int stx_guided_style_loss(const float* z, const float* wts, float w_max, const float* target,
+                          float* g_out, float* coef, float* loss_r, int b, int c, int hw, int R,
+                          const float* lambda, float weight, const float* z_amax, void* ws,
+                          size_t ws_bytes, void* stream);
+/* dz[b] (+)= s sum_r wts[r] o (A[b][r] z[b]),  s = *acc_scale_dev (or 1 if NULL): the
+ * backward of the guided style loss in one pass over z whatever R is (z viewed
+ * [b][c][h][w], c <= 512, coef as stx_guided_style_loss writes it).  With both amax groups
+ * (z_amax >= max|z|, coef_amax >= max|coef|) the products run on the fp16 hi/lo split
+ * MFMA, else on the fp32 MFMA.  accumulate = 1 adds onto dz. */
+int stx_guided_gram_bwd(const float* coef, const float* z, const float* wts, float* dz, int b,
+                        int c, int h, int w, int R, const float* acc_scale_dev, int accumulate,
+                        const float* z_amax, const float* coef_amax, void* stream);
 
 /* Sum-of-squared-difference reductions (ContentLoss / FeatureReconstructionLoss):
  *   s = sum((f(a) - f(b))^2), f = relu if relu_inputs else identity

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("STX_LIB", os.path.join(_HERE, "libstx.so"))
 STX_IN_RAW, STX_IN_RELU, STX_IN_RELU_POOL2, STX_IN_UPSAMPLE2, STX_IN_DILATE2 = range(5)
 STX_AMAX_SLOTS = 32  # an "amax" is a group of 32 floats whose max is the value (stx.h)
 STX_GRAM_GROUP = 8  # fused Gram partials per in-kernel group sum (stx_conv_params.gram_cnt)
-STX_ABI_VERSION = 8 # include/stx.h: the library must report the same revision
+STX_ABI_VERSION = 9 # include/stx.h: the library must report the same revision
 
 
 def knob(name: str, default: str) -> str:
@@ -102,6 +102,7 @@ class GramFinJob(C.Structure):
 
 
 STX_FIN_MAX = 8
+STX_GUIDE_MAX = 4  # regions of a guided Gram (include/stx.h)
 
 
 # name -> (restype, argtypes); every symbol include/stx.h declares
@@ -169,6 +170,11 @@ SIGNATURES = {
                                                          C.POINTER(GramFinJob), vp]),
     "stx_gram_finalize_batch": (i32, [C.POINTER(GramFinJob), i32, vp]),
     "stx_gram_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, f32, i32, vp]),
+    "stx_guided_style_ws": (sz, [i32, i32, i32, i32]),
+    "stx_guided_style_loss": (i32, [vp, vp, f32, vp, vp, vp, vp, i32, i32, i32, i32,
+                                    C.POINTER(f32), f32, vp, vp, sz, vp]),
+    "stx_guided_gram_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp,
+                                  vp]),
     "stx_mse_ws": (sz, [i64]),
     "stx_mse": (i32, [vp, vp, i64, i32, i32, vp, vp, f32, vp, sz, vp]),
     "stx_diff_scale": (i32, [vp, vp, vp, i64, f32, vp, vp, i32, i32, vp]),

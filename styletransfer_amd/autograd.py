@@ -394,6 +394,25 @@ class StyleLossFn(torch.autograd.Function):
         return ops.gram_bwd(coef, z, acc_scale=_c(g.reshape(1))), None
 
 
+class GuidedStyleLossFn(torch.autograd.Function):
+    """sum_r lam[r] * mean((G_r(z) - T_r)^2), G_r the Gram weighted by region r's pixel
+    weights (ops.guided_style_loss)."""
+
+    @staticmethod
+    def forward(ctx, z, wts, targets, lam):
+        z, wts = _c(z), _c(wts.detach())
+        loss_r, coef = ops.guided_style_loss(z, wts, _c(targets.detach()), lam, weight=1.0)
+        ctx.save_for_backward(z, wts, coef)
+        ctx.loss_r = loss_r
+        w = torch.tensor([float(v) for v in lam], device=z.device, dtype=torch.float32)
+        return (loss_r * w).sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        z, wts, coef = ctx.saved_tensors
+        return ops.guided_gram_bwd(coef, z, wts, acc_scale=_c(g.reshape(1))), None, None, None
+
+
 class MSELossFn(torch.autograd.Function):
     """F.mse_loss(x, target) (ContentLoss.forward, stransfer/network.py:155-164)."""
 

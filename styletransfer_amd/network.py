@@ -109,6 +109,25 @@ class StyleLoss(nn.Module):
             self.target = A.GramFn.apply(target.detach().contiguous()).detach()
 
 
+class GuidedStyleLoss(nn.Module):
+    """The style loss of one tap under spatial control (Gatys et al. 2017, "Controlling
+    Perceptual Factors in Neural Style Transfer"): region r has its own target Gram
+    targets[r] [c][c] and pixel weights wts[r] (the tap's entry of vgg.guides_for_taps,
+    [R][h][w]); `.loss` = sum_r region_weights[r] * mean((G_r(input) - targets[r])^2)."""
+
+    def __init__(self, targets: torch.Tensor, wts: torch.Tensor, region_weights=None):
+        super().__init__()
+        self.targets = _dev(targets.detach()).contiguous()
+        self.wts = _dev(wts.detach()).contiguous()
+        R = self.wts.shape[0]
+        self.region_weights = [1.0] * R if region_weights is None else list(region_weights)
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        self.loss = A.GuidedStyleLossFn.apply(input, self.wts, self.targets,
+                                              self.region_weights)
+        return input
+
+
 class ContentLoss(nn.Module):
     """stransfer/network.py:134-164."""
 
@@ -370,6 +389,20 @@ class StyleNetwork(nn.Module):
         targets = [l.target for l, _ in self.style_losses]  # set in __init__, as the reference
         eng = V.GatysEngine(self.features(), None, _dev(content_image), style_weight,
                             content_weight, targets=targets)
+        eng.run(steps, graph=graph)
+        return eng.x
+
+    def train_gatys_guided(self, style_images, content_image, guides, style_guides=None,
+                           region_weights=None, steps=500, style_weight=100_000,
+                           content_weight=1, graph=True) -> torch.Tensor:
+        """Region-guided Gatys optimisation (Adam, one hipGraph replay per iteration):
+        region r of the canvas (guides[r], an HxW map in [0, 1]) takes the style of
+        style_images[r], optionally only of the part style_guides[r] selects; pixels no
+        guide covers get the content loss only (vgg.GuidedGatysEngine)."""
+        eng = V.GuidedGatysEngine(self.features(), [_dev(s) for s in style_images],
+                                  _dev(content_image), guides, style_guides=style_guides,
+                                  region_weights=region_weights, style_weight=style_weight,
+                                  content_weight=content_weight)
         eng.run(steps, graph=graph)
         return eng.x
 

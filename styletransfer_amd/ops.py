@@ -19,7 +19,7 @@ from ._native import ConvParams, check, lib
 __all__ = [
     "conv_weight_dims", "conv_weight_prep", "conv_weight_prep16", "split_eligible", "amax",
     "conv2d", "conv_out_hw", "conv2d_wgrad",
-    "bias_grad", "gram", "style_loss", "gram_bwd", "mse", "diff_scale", "loss_combine",
+    "bias_grad", "gram", "style_loss", "gram_bwd", "guided_style_loss", "guided_gram_bwd", "mse", "diff_scale", "loss_combine",
     "maxpool2x2", "maxpool2x2_bwd", "relupool_bwd", "relu", "relu_bwd", "adam_step",
     "instnorm_fwd", "instnorm_bwd", "cin_mix", "upsample2x", "upsample2x_bwd", "tv_loss",
     "temporal_loss", "temporal_loss_bwd",
@@ -941,6 +941,78 @@ def gram_bwd(coef, z, dz=None, acc_scale=None, mask=None, aux=None, aux_scale=0.
     check(lib().stx_gram_bwd(coef.data_ptr(), z.data_ptr(), dz.data_ptr(), b, c, h, w,
                              _p(acc_scale), _p(mask), _p(aux), float(aux_scale), int(accumulate),
                              _stream()), "stx_gram_bwd")
+    return dz
+
+
+# ----------------------------------------------------------------------- guided gram
+def guided_style_loss(z, wts, targets, lam, weight=1.0, z_amax=None, w_max=None, g_out=None,
+                      coef=None, loss_r=None, want_coef=True, ws=None):
+    """Region-weighted style loss (stx_guided_style_loss): R regions with pixel weights
+    wts [R][hw] (each row normalised to sum hw), targets [R][c][c], lam = R host floats.
+    Returns (loss_r [R] device floats, coef [b][R][cpad][cpad]) with
+    coef[b][r] = weight * lam[r] * d loss_r / dG . 2/(c hw), the operator guided_gram_bwd
+    applies.  z_amax (amax group >= max|z|) selects the fp16 hi/lo split MFMA where
+    hw % 8 == 0.  w_max (host float >= wts.max()) is read from wts when absent (a host
+    sync: pass it inside a captured iteration).  ws: a uint8 device buffer >=
+    stx_guided_style_ws to use instead of the shared scratch."""
+    _req(z, "z")
+    _req(wts, "wts")
+    _req(targets, "targets")
+    b, c = z.shape[:2]
+    hw = z[0, 0].numel()
+    R = wts.shape[0]
+    if wts.numel() != R * hw:
+        raise ValueError(f"wts {tuple(wts.shape)} does not cover {hw} pixels per region")
+    if targets.numel() != R * c * c:
+        raise ValueError(f"targets {tuple(targets.shape)} is not ({R},{c},{c})")
+    lam = [float(v) for v in lam]
+    if len(lam) != R:
+        raise ValueError(f"{len(lam)} region weights for {R} regions")
+    if w_max is None:
+        w_max = float(wts.max())
+    if loss_r is None:
+        loss_r = torch.empty(R, device=z.device, dtype=torch.float32)
+    if want_coef and coef is None:
+        cp = coef_pitch(c)
+        coef = torch.empty((b, R, cp, cp), device=z.device, dtype=torch.float32)
+    L = lib()
+    need = L.stx_guided_style_ws(b, c, hw, R)
+    if ws is not None:
+        assert ws.numel() >= need > 0, (ws.numel(), need)
+        wp, wn = ws.data_ptr(), ws.numel()
+    else:
+        wp, wn = WS.get(need, z.device)
+    arr = (C.c_float * max(R, 1))(*lam)
+    check(L.stx_guided_style_loss(z.data_ptr(), wts.data_ptr(), float(w_max), targets.data_ptr(),
+                                  _p(g_out), _p(coef) if want_coef else None, loss_r.data_ptr(),
+                                  b, c, hw, R, arr, float(weight), _p(z_amax), wp, wn,
+                                  _stream()), "stx_guided_style_loss")
+    return loss_r, (coef if want_coef else None)
+
+
+def guided_gram_bwd(coef, z, wts, dz=None, acc_scale=None, accumulate=False, z_amax=None,
+                    coef_amax=None):
+    """dz (+)= s * sum_r wts[r] o (coef[:, r] . z) (stx_guided_gram_bwd), one pass over z.
+    With z_amax and coef_amax (amax groups) the products run on the fp16 hi/lo split MFMA,
+    else on the fp32 MFMA."""
+    _req(z, "z")
+    _req(wts, "wts")
+    _req(coef, "coef")
+    b, c, h, w = z.shape
+    R = wts.shape[0]
+    cp = coef_pitch(c)
+    if wts.numel() != R * h * w or coef.numel() != b * R * cp * cp:
+        raise ValueError(f"wts {tuple(wts.shape)} / coef {tuple(coef.shape)} do not match z "
+                         f"{tuple(z.shape)} with {R} regions")
+    if dz is None:
+        if accumulate:
+            raise ValueError("accumulate needs dz")
+        dz = torch.empty_like(z)
+    _req(dz, "dz")
+    assert dz.shape == z.shape, (dz.shape, z.shape)
+    check(lib().stx_guided_gram_bwd(coef.data_ptr(), z.data_ptr(), wts.data_ptr(), dz.data_ptr(),
+                                    b, c, h, w, R, _p(acc_scale), int(accumulate), _p(z_amax),
+                                    _p(coef_amax), _stream()), "stx_guided_gram_bwd")
     return dz
 
 

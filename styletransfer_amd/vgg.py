@@ -683,3 +683,248 @@ class GatysLBFGS:
         for _ in range(steps):
             self.step()
         return self.x
+
+
+# ---------------------------------------------------------------------------------------
+# Region-guided Gatys transfer (Gatys et al. 2017, "Controlling Perceptual Factors in
+# Neural Style Transfer", spatial control): R regions of the canvas, each with its own
+# style.  For a tap with features z [b][c][h][w], hw = h w, and region weights
+# wts [R][hw] >= 0 normalised to sum hw per region:
+#     G[b][r] = 1/(c hw) sum_p wts[r][p] z[b][:,p] z[b][:,p]^T
+#     loss_r  = 1/(b c c) sum (G[b][r] - T[r])^2,    loss = sum_r lambda_r loss_r
+#     dz[b]   = sum_r wts[r] o (A[b][r] z[b]),  A[b][r] = lambda_r 4/(b c^3 hw) (G[b][r] - T[r])
+# (ops.guided_style_loss / ops.guided_gram_bwd).  R = 1 with all-ones weights is StyleLoss.
+TAP_POOLS = (0, 0, 1, 1, 2)  # 2x2 average pools between the guide and each tap's map
+
+
+def guides_for_taps(mask_hw):
+    """The five per-tap weight maps of one region's guide (an HxW map in [0, 1]), or of R
+    guides at once ([R][H][W] -> five [R][h_l][w_l] tensors).  Taps 1-2 use the guide as
+    is, taps 3-4 avg_pool2d(., 2) of it, tap 5 pools once more (floor mode, as the VGG
+    max pools: 37x41 -> 18x20 -> 9x10); each map is then normalised to sum h_l w_l.
+
+    The Gram weight is the pooled guide itself: with feature maps multiplied by a guide
+    T_l as in the paper, the Gram matrix weights each pixel by T_l^2 -- so the map used
+    here is the paper's T_l^2, not T_l.  A map that sums to 0 at any tap raises
+    ValueError naming the region."""
+    m = torch.as_tensor(mask_hw).detach().to("cpu", torch.float64)
+    single = m.dim() == 2
+    if single:
+        m = m[None]
+    if m.dim() != 3:
+        raise ValueError(f"guide must be [H][W] or [R][H][W], got {tuple(m.shape)}")
+    if bool((m < 0).any()):
+        raise ValueError("guide values must be non-negative")
+    maps, cur, pooled = [], m, 0
+    for l, k in enumerate(TAP_POOLS):
+        while pooled < k:
+            if min(cur.shape[1:]) < 2:
+                raise ValueError(f"guide {tuple(m.shape[1:])} is too small for tap {l + 1}")
+            cur = torch.nn.functional.avg_pool2d(cur[None], 2)[0]
+            pooled += 1
+        s = cur.sum(dim=(1, 2))
+        for r in range(cur.shape[0]):
+            if not float(s[r]) > 0.0:
+                raise ValueError(f"guide of region {r} sums to 0 at tap {l + 1}")
+        hw = cur.shape[1] * cur.shape[2]
+        w = (cur * (hw / s)[:, None, None]).to(torch.float32)
+        maps.append(w[0] if single else w)
+    return maps
+
+
+def _guided_gram(z, wmap):
+    """[c][c] guided Gram of one image's features under one weight map (b = 1, R = 1)."""
+    c = z.shape[1]
+    wts = wmap.reshape(1, -1).to(z.device, torch.float32).contiguous()
+    g = torch.empty((1, 1, c, c), device=z.device, dtype=torch.float32)
+    zero = torch.zeros((1, c, c), device=z.device, dtype=torch.float32)
+    ops.guided_style_loss(z, wts, zero, [1.0], g_out=g, want_coef=False, z_amax=ops.amax(z))
+    return g[0, 0]
+
+
+def guided_style_targets(feat: VGGFeatures, style_images, style_guides=None):
+    """T_l [R][c_l][c_l] per tap: region r's target is the guided Gram of style_images[r]'s
+    features under style_guides[r] (an HxW map of that image's size), or, with no guide,
+    the Gram of the whole image (feat.style_targets' value).  The style images need not
+    have the content's size, nor each other's."""
+    R = len(style_images)
+    if style_guides is None:
+        style_guides = [None] * R
+    if len(style_guides) != R:
+        raise ValueError(f"{len(style_guides)} style guides for {R} style images")
+    per_region = []
+    for r, (img, guide) in enumerate(zip(style_images, style_guides)):
+        img = img.to(feat.device, torch.float32).contiguous()
+        zs = feat.forward(img)
+        if guide is None:
+            per_region.append([ops.gram(z)[0] for z in zs])
+            continue
+        if tuple(guide.shape[-2:]) != tuple(img.shape[-2:]):
+            raise ValueError(f"style guide {r} is {tuple(guide.shape[-2:])}, its image "
+                             f"{tuple(img.shape[-2:])}")
+        try:
+            maps = guides_for_taps(guide.reshape(guide.shape[-2:]))
+        except ValueError as e:
+            raise ValueError(f"style guide of region {r}: {e}") from None
+        per_region.append([_guided_gram(z, w) for z, w in zip(zs, maps)])
+    return [torch.stack([per_region[r][l] for r in range(R)]).contiguous() for l in range(5)]
+
+
+class GuidedGatysEngine:
+    """GatysEngine under spatial control: region r of the canvas (guides[r], an HxW map
+    in [0, 1] of the content's size) is drawn to the style of style_images[r]; pixels no
+    guide covers get the content loss only.
+
+        total = style_weight * sum_l sum_r region_weights[r] * loss_{l,r}
+                + content_weight * mse(Z4, C4)
+
+    One iteration (forward, backward, Adam on the image) is one hipGraph replay of the
+    unfused chain: the five convs with ops.guided_style_loss at each tap, then per tap
+    ops.guided_gram_bwd accumulated onto the data gradient that reaches it."""
+
+    def __init__(self, feat: VGGFeatures, style_images, content_image, guides, style_guides=None,
+                 region_weights=None, style_weight=100_000, content_weight=1, lr=1e-3,
+                 betas=(0.9, 0.999), eps=1e-8, init=None):
+        dev = feat.device
+        self.feat = feat
+        guides = torch.stack([torch.as_tensor(g).reshape(g.shape[-2:]) for g in guides]) \
+            if isinstance(guides, (list, tuple)) else torch.as_tensor(guides)
+        if guides.dim() == 2:
+            guides = guides[None]
+        R = guides.shape[0]
+        if not 1 <= R <= N.STX_GUIDE_MAX:
+            raise ValueError(f"1 to {N.STX_GUIDE_MAX} regions supported, got {R}")
+        if len(style_images) != R:
+            raise ValueError(f"{len(style_images)} style images for {R} guides")
+        self.content = content_image.to(dev, torch.float32).contiguous()
+        if tuple(guides.shape[1:]) != tuple(self.content.shape[2:]):
+            raise ValueError(f"guides are {tuple(guides.shape[1:])}, the content image "
+                             f"{tuple(self.content.shape[2:])}")
+        self.R = R
+        self.lam = [1.0] * R if region_weights is None else [float(v) for v in region_weights]
+        if len(self.lam) != R:
+            raise ValueError(f"{len(self.lam)} region weights for {R} regions")
+        # set-up, in torch, outside the captured iteration
+        maps = guides_for_taps(guides)
+        self.wts = [m.reshape(R, -1).to(dev).contiguous() for m in maps]
+        self.w_max = [float(m.max()) for m in maps]
+        self.targets = guided_style_targets(feat, style_images, style_guides)
+        self.c4 = content_target(feat, self.content).clone()
+        src = self.content if init is None else init.to(dev, torch.float32)
+        self.x = src.clone().contiguous()
+        self.grad = torch.zeros_like(self.x)
+        self.m = torch.zeros_like(self.x)
+        self.v = torch.zeros_like(self.x)
+        self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.adam_ws = torch.zeros(16, dtype=torch.float32, device=dev)
+        self.lr, self.betas, self.eps = lr, betas, eps
+        self.sw, self.cw = float(style_weight), float(content_weight)
+        self.total = torch.zeros((), device=dev, dtype=torch.float32)
+        # [5][R] region losses, then the content loss
+        self.vals = torch.zeros(5 * R + 1, device=dev, dtype=torch.float32)
+        self.partial = torch.zeros(2, device=dev, dtype=torch.float32)
+        self.st = LossState()
+        self.st.amax = torch.zeros(LOSS_AMAX_GROUPS * N.STX_AMAX_SLOTS, device=dev,
+                                   dtype=torch.float32)
+        self.coef = [None] * 5
+        self.coef_amax = torch.zeros(5 * N.STX_AMAX_SLOTS, device=dev, dtype=torch.float32)
+        self.lws = [None] * 5
+        self.scratch = {}
+        self.graph = None
+        self.adam = True  # (the tests run an iteration without the update)
+
+    # ------------------------------------------------------------------ one iteration
+    def _forward(self):
+        st, R = self.st, self.R
+        am = st.amax
+        if not st.amax_cleared:
+            am.zero_()
+        st.amax_cleared = False
+        sp = self.feat.wt16[1] is not None  # split kernels in use: the convs emit max|Z_l|
+        L = N.lib()
+
+        def on_layer(l, z):
+            b_, c_ = z.shape[:2]
+            need = L.stx_guided_style_ws(b_, c_, z[0, 0].numel(), R)
+            if self.lws[l] is None or self.lws[l].numel() < need:
+                self.lws[l] = torch.empty(need, device=z.device, dtype=torch.uint8)
+            _, self.coef[l] = ops.guided_style_loss(
+                z, self.wts[l], self.targets[l], self.lam, weight=self.sw,
+                z_amax=slot(am, l + 1) if sp else None, w_max=self.w_max[l], coef=self.coef[l],
+                loss_r=self.vals[l * R:(l + 1) * R], ws=self.lws[l])
+            if sp:  # max|A| of the tap: the backward's split scale
+                ops.amax(self.coef[l], out=slot(self.coef_amax, l))
+            if l == CONTENT_CONV:
+                ops.mse(z, self.c4, out=self.vals[5 * R:5 * R + 1])
+
+        st.z = self.feat.forward(self.x, 5, st.z if st.z else None, amax=am, pools=st.pools,
+                                 on_layer=on_layer)
+        w = [self.sw * self.lam[r] for _ in range(5) for r in range(R)] + [self.cw]
+        if len(w) <= 16:
+            ops.loss_combine(self.vals, w, self.total)
+        else:  # stx_loss_combine takes 16 values
+            ops.loss_combine(self.vals[:16], w[:16], self.partial[0:1])
+            ops.loss_combine(self.vals[16:], w[16:], self.partial[1:2])
+            ops.loss_combine(self.partial, [1.0, 1.0], self.total)
+
+    def _backward(self):
+        feat, st, sc = self.feat, self.st, self.scratch
+        z, am = st.z, st.amax
+        B = z[0].shape[0]
+        sp = feat.wt16[1] is not None
+
+        def buf(name, shape):
+            t = sc.get(name)
+            if t is None or tuple(t.shape) != tuple(shape):
+                t = torch.empty(shape, device=z[0].device, dtype=torch.float32)
+                sc[name] = t
+            return t
+
+        def guided(l, dz, accumulate=True):
+            return ops.guided_gram_bwd(self.coef[l], z[l], self.wts[l].view(self.R, -1), dz=dz,
+                                       accumulate=accumulate,
+                                       z_amax=slot(am, l + 1) if sp else None,
+                                       coef_amax=slot(self.coef_amax, l) if sp else None)
+
+        def bound(t, k):  # max|t| into amax group k: the next split data gradient's scale
+            return ops.amax(t, out=slot(am, k)) if sp else None
+
+        dz5 = guided(4, buf("dz5", z[4].shape), accumulate=False)
+        dp2 = feat.dgrad(4, dz5, buf("dp2", (B, 128, z[3].shape[2] // 2, z[3].shape[3] // 2)),
+                         in_amax=bound(dz5, 6))
+        dz4 = ops.relupool_bwd(dp2, z[3], out=buf("dz4", z[3].shape))
+        guided(3, dz4)
+        ops.diff_scale(z[3], self.c4, self.cw * 2.0 / z[3].numel(), out=dz4, accumulate=True)
+        dz3 = feat.dgrad(3, dz4, buf("dz3", z[2].shape), mask=z[2], in_amax=bound(dz4, 7))
+        guided(2, dz3)
+        dp1 = feat.dgrad(2, dz3, buf("dp1", (B, 64, z[1].shape[2] // 2, z[1].shape[3] // 2)),
+                         in_amax=bound(dz3, 8))
+        dz2 = ops.relupool_bwd(dp1, z[1], out=buf("dz2", z[1].shape))
+        guided(1, dz2)
+        dz1 = feat.dgrad(1, dz2, buf("dz1", z[0].shape), mask=z[0], in_amax=bound(dz2, 9))
+        guided(0, dz1)
+        feat.dgrad(0, dz1, self.grad, in_amax=bound(dz1, 10))
+
+    def _iteration(self):
+        self._forward()
+        self._backward()
+        if self.adam:
+            # the Adam launch also zeroes the amax groups for the next iteration's forward
+            ops.adam_step(self.x, self.grad, self.m, self.v, self.step_dev, self.adam_ws,
+                          self.lr, self.betas[0], self.betas[1], self.eps, clear=self.st.amax)
+            self.st.amax_cleared = True
+
+    capture = GatysEngine.capture
+    step = GatysEngine.step
+    run = GatysEngine.run
+
+    def region_losses(self):
+        """[5][R]: loss_{l,r} of the last forward (a view of the device loss vector)."""
+        return self.vals[:5 * self.R].view(5, self.R)
+
+    def losses(self):
+        """[style x5, content, feature] of the last forward, as GatysEngine.losses(): style_l
+        = sum_r region_weights[r] loss_{l,r}; the feature loss is not part of this engine."""
+        lam = torch.tensor(self.lam, device=self.vals.device, dtype=torch.float32)
+        style = (self.region_losses() * lam).sum(dim=1)
+        return torch.cat([style, self.vals[5 * self.R:], style.new_zeros(1)])
