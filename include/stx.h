@@ -178,7 +178,9 @@ const char* stx_last_error_string(void);
 /* The ABI revision of this header (STX_ABI_VERSION): a host binding refuses a library of
  * another revision rather than pass arguments whose meaning changed (round 6:
  * stx_instnorm_bwd's second argument is beta, not y; 7: stx_conv_params.unpool_out;
- * 9: the guided Gram entry points). */
+ * 9: the guided Gram entry points).  The revision moves only when an existing entry
+ * point or struct changes meaning; entry points that are merely added (the colour
+ * control pair below) do not bump it -- a binding finds a missing symbol at load. */
 #define STX_ABI_VERSION 9
 int stx_abi_version(void);
 
@@ -376,6 +378,38 @@ int stx_guided_style_loss(const float* z, const float* wts, float w_max, const f
 int stx_guided_gram_bwd(const float* coef, const float* z, const float* wts, float* dz, int b,
                         int c, int h, int w, int R, const float* acc_scale_dev, int accumulate,
                         const float* z_amax, const float* coef_amax, void* stream);
+
+/* Colour control -- Gatys et al. 2017, "Controlling Perceptual Factors in Neural Style
+ * Transfer", section 5 (the reference project has no such feature).
+ *
+ * stx_color_stats: the statistics colour matching needs (section 5.2, "colour histogram
+ * matching": the style image's RGB mean and covariance are mapped onto the content
+ * image's), and from which luminance mean / variance follow (section 5.1).  x
+ * [n][3][h][w]; stats receives 9 doubles per image: mean[3], then the upper triangle
+ * [rr, rg, rb, gg, gb, bb] of the population covariance E[x x^T] - mu mu^T.  fp64
+ * accumulation, a fixed block count per image and fixed-order sums: bit-reproducible, and
+ * image k's result does not depend on n.  ws >= stx_color_stats_ws(n, h, w) bytes, 16-byte
+ * aligned (0: unsupported dims; n <= 65535).  16-byte loads when h w % 4 == 0 and x is
+ * 16-byte aligned, scalar loads otherwise. */
+size_t stx_color_stats_ws(int n, int h, int w);
+int stx_color_stats(const float* x, double* stats, int n, int h, int w, void* ws,
+                    size_t ws_bytes, void* stream);
+/* stx_color_affine: a 3x3 colour transform per pixel over [n][3][h][w],
+ *   out[c] = clamp_c( base[c] + sum_d M[c][d] (x[d] - base[d]) + b[c] )
+ * evaluated as t[d] = x[d] - base[d];  v = fma(M[c][0], t[0], b[c]);  v = fma(M[c][1],
+ * t[1], v);  v = fma(M[c][2], t[2], v);  out[c] = base[c] + v, then min(max(., lo[c]),
+ * hi[c]) -- bit-stable.  It serves the recolouring of the style image (section 5.2: M =
+ * Sigma_c^1/2 Sigma_s^-1/2, b = mu_c - M mu_s), the luminance image of section 5.1 (M's
+ * rows all the luma weights) and the luminance merge that gives the stylised luminance
+ * the content's chroma (section 5.1; base = the content image: YIQ^-1 maps Y to (1,1,1),
+ * so replacing base's luminance by x's adds the luminance difference to every channel).
+ * base may be NULL (reads as zeros); b may be NULL (zeros); lo / hi are per-channel clamp
+ * bounds, both NULL for no clamp.  M [3][3] row-major, b, lo, hi are HOST arrays read
+ * before the call returns and passed as kernel arguments (a captured graph bakes them
+ * in).  out may alias x or base. */
+int stx_color_affine(const float* x, const float* base, float* out, int n, int h, int w,
+                     const float* M, const float* b, const float* lo, const float* hi,
+                     void* stream);
 
 /* Sum-of-squared-difference reductions (ContentLoss / FeatureReconstructionLoss):
  *   s = sum((f(a) - f(b))^2), f = relu if relu_inputs else identity

@@ -175,6 +175,10 @@ SIGNATURES = {
                                     C.POINTER(f32), f32, vp, vp, sz, vp]),
     "stx_guided_gram_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp,
                                   vp]),
+    "stx_color_stats_ws": (sz, [i32, i32, i32]),
+    "stx_color_stats": (i32, [vp, vp, i32, i32, i32, vp, sz, vp]),
+    "stx_color_affine": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(f32), C.POINTER(f32),
+                               C.POINTER(f32), C.POINTER(f32), vp]),
     "stx_mse_ws": (sz, [i64]),
     "stx_mse": (i32, [vp, vp, i64, i32, i32, vp, vp, f32, vp, sz, vp]),
     "stx_diff_scale": (i32, [vp, vp, vp, i64, f32, vp, vp, i32, i32, vp]),

@@ -79,7 +79,9 @@ def train_multi(style_image_paths, name, epochs, batch_size, content_weight, sty
                    "first style")
 @click.option("-o", "--out-dir", default="results/",
               help="The results directory where the converted image will be saved")
-def convert_image_multi(image_path, name, mix, out_dir):
+@click.option("--preserve-color", is_flag=True,
+              help="Keep the image's colours: only the luminance of the result is used")
+def convert_image_multi(image_path, name, mix, out_dir, preserve_color):
     """Convert IMAGE-PATH with the multi-style network NAME, blending its styles by --mix."""
     try:
         names = network.MultiStyleTransformNet.load_style_names(name)
@@ -88,7 +90,8 @@ def convert_image_multi(image_path, name, mix, out_dir):
         raise click.UsageError(str(e))
     sty = network.MultiStyleTransformNet([torch.rand([3, 8, 8])] * len(names),
                                          style_names=names)
-    sty.process_image(image_path=image_path, name=name, mix=weights, out_dir=out_dir)
+    sty.process_image(image_path=image_path, name=name, mix=weights, out_dir=out_dir,
+                      preserve_color=preserve_color)
 
 
 @fast_st.command()
@@ -96,7 +99,10 @@ def convert_image_multi(image_path, name, mix, out_dir):
 @click.argument("style-name")
 @click.option("-o", "--out-dir", default="results/",
               help="The results directory where the converted image will be saved")
-def convert_image(image_path, style_name, out_dir):
+@click.option("--preserve-color", is_flag=True,
+              help="Keep the image's colours: only the luminance of the result is used")
+def convert_image(image_path, style_name, out_dir, preserve_color):
     """Convert IMAGE-PATH with the network pretrained on STYLE-NAME (data/models/)."""
     sty = network.ImageTransformNet(torch.rand([3, 255, 255]))
-    sty.process_image(image_path=image_path, style_name=style_name, out_dir=out_dir)
+    sty.process_image(image_path=image_path, style_name=style_name, out_dir=out_dir,
+                      preserve_color=preserve_color)

@@ -46,7 +46,12 @@ def mask_loader(path: str, imsize=None) -> torch.Tensor:
               help="The weight we will assign to the content loss during the optimization")
 @click.option("-sw", "--style-weight", default=100_000,
               help="The weight we will assign to the style loss during the optimization")
-def gatys_guided(content_image_path, regions, out_name, steps, content_weight, style_weight):
+@click.option("--preserve-color", type=click.Choice(["match", "luminance"]), default=None,
+              help="Keep the content image's colours: match = recolour every region's style "
+                   "image to the whole content image's mean and covariance first; luminance "
+                   "= transfer on luminance only, then restore the content's chroma")
+def gatys_guided(content_image_path, regions, out_name, steps, content_weight, style_weight,
+                 preserve_color):
     """Gatys style transfer with one style per masked region of the image."""
     if len(regions) > MAX_REGIONS:
         raise click.UsageError(f"at most {MAX_REGIONS} regions (-r), got {len(regions)}")
@@ -59,10 +64,17 @@ def gatys_guided(content_image_path, regions, out_name, steps, content_weight, s
                     for _, _, sm in specs]
     if all(g is None for g in style_guides):
         style_guides = None
+    finish = None
+    if preserve_color is not None:
+        from .. import color
+        style_images, content_image, finish = color.prepare(style_images, content_image,
+                                                            preserve_color)
     net = network.StyleNetwork(style_images[0], content_image)
     converted = net.train_gatys_guided(style_images, content_image, guides,
                                        style_guides=style_guides, style_weight=style_weight,
                                        content_weight=content_weight, steps=steps)
+    if finish is not None:
+        converted = finish(converted)
     out_dir = os.path.join(root, "results")
     os.makedirs(out_dir, exist_ok=True)
     out_file = os.path.join(out_dir, out_name)

@@ -55,7 +55,9 @@ def train(style_image_path, epochs, batch_size, content_weight, style_weight, te
 @click.argument("style-name")
 @click.option("-o", "--out-dir", default="results/")
 @click.option("--fps", default=24.0)
-def convert_video(video_path, style_name, out_dir, fps):
+@click.option("--preserve-color", is_flag=True,
+              help="Keep each frame's colours: only the luminance of the result is used")
+def convert_video(video_path, style_name, out_dir, fps, preserve_color):
     """Convert a video with a pretrained video network (stransfer/clis/video_st.py).
     VIDEO_PATH: a video file (needs imageio), a directory of frames or a .npy array."""
     import torch
@@ -63,5 +65,5 @@ def convert_video(video_path, style_name, out_dir, fps):
     from .. import network
     sty = network.VideoTransformNet(torch.rand([3, 255, 255]))  # as the reference CLI
     out = sty.process_video(video_path=video_path, style_name=style_name, out_dir=out_dir,
-                            fps=fps)
+                            fps=fps, preserve_color=preserve_color)
     click.echo(f"stylised video: {out}")

@@ -605,13 +605,18 @@ class ImageTransformNet(nn.Sequential):
         LOGGER.info("Average test loss: %.8f", float(avg))
         return avg
 
-    def process_image(self, image_path: str, style_name="nsp", out_dir="results/") -> None:
-        """stransfer/network.py:798-832."""
+    def process_image(self, image_path: str, style_name="nsp", out_dir="results/",
+                      preserve_color=False) -> None:
+        """stransfer/network.py:798-832.  preserve_color: keep the image's colours (the
+        luminance merge of color.merge_luminance, one launch after the forward)."""
         self.load_state_dict(_load_latest_model_weigths(model_name="fast_st",
                                                         style_name=style_name))
         image = img_utils.image_loader(os.path.join(constants.PROJECT_ROOT_PATH, image_path))
         with torch.no_grad():
             out = self(image)
+        if preserve_color:
+            from . import color
+            out = color.merge_luminance(out, image)
         out_dir = os.path.join(constants.PROJECT_ROOT_PATH, out_dir)
         os.makedirs(out_dir, exist_ok=True)
         img_utils.imshow(out, path=os.path.join(out_dir, f"converted_fast_st_{style_name}.png"))
@@ -758,15 +763,20 @@ class MultiStyleTransformNet(ImageTransformNet):
             raise AssertionError(f"There are no multi-style weights named {name!r} in {root}")
         self.load_state_dict(adaptive_torch_load(os.path.join(root, found[-1])))
 
-    def process_image(self, image_path: str, name="nsp", mix=None, out_dir="results/"):
+    def process_image(self, image_path: str, name="nsp", mix=None, out_dir="results/",
+                      preserve_color=False):
         """Convert an image with the latest checkpoint of `name`; mix: None (the first
-        style), a style index, or weights [S] (parse_mix).  Returns the output tensor."""
+        style), a style index, or weights [S] (parse_mix).  preserve_color: keep the
+        image's colours (color.merge_luminance).  Returns the output tensor."""
         self.load_latest(name)
         image = img_utils.image_loader(os.path.join(constants.PROJECT_ROOT_PATH, image_path))
         if mix is not None and not isinstance(mix, int):
             mix = torch.as_tensor(mix, dtype=torch.float32)
         with torch.no_grad():
             out = self(image, style=mix)
+        if preserve_color:
+            from . import color
+            out = color.merge_luminance(out, image)
         out_dir = os.path.join(constants.PROJECT_ROOT_PATH, out_dir)
         os.makedirs(out_dir, exist_ok=True)
         img_utils.imshow(out, path=os.path.join(out_dir, f"converted_fast_mst_{name}.png"))
@@ -797,14 +807,16 @@ class VideoTransformNet(ImageTransformNet):
             self.has_external_weights = False
 
     def process_video(self, video_path: str, style_name="nsp", working_dir="workdir/",
-                      out_dir="results/", fps=24.0):
+                      out_dir="results/", fps=24.0, preserve_color=False):
         """stransfer/network.py:1071-1158 on the graph-captured per-frame engine
         (styletransfer_amd/video.py); frames come from imageio when installed, or from
-        a directory of frames / a .npy frame array."""
+        a directory of frames / a .npy frame array.  preserve_color: every output frame
+        keeps its input frame's colours (the luminance merge inside the frame graph)."""
         from . import video
         self.load_state_dict(_load_latest_model_weigths(model_name="video_st",
                                                         style_name=style_name))
-        return video.process_video(self, video_path, style_name, working_dir, out_dir, fps)
+        return video.process_video(self, video_path, style_name, working_dir, out_dir, fps,
+                                   preserve_color=preserve_color)
 
     def get_temporal_loss(self, old_content, old_stylized, current_content, current_stylized,
                           temporal_weight=1) -> torch.Tensor:

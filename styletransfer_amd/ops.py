@@ -22,7 +22,7 @@ __all__ = [
     "bias_grad", "gram", "style_loss", "gram_bwd", "guided_style_loss", "guided_gram_bwd", "mse", "diff_scale", "loss_combine",
     "maxpool2x2", "maxpool2x2_bwd", "relupool_bwd", "relu", "relu_bwd", "adam_step",
     "instnorm_fwd", "instnorm_bwd", "cin_mix", "upsample2x", "upsample2x_bwd", "tv_loss",
-    "temporal_loss", "temporal_loss_bwd",
+    "temporal_loss", "temporal_loss_bwd", "color_stats", "color_affine",
 ]
 
 
@@ -1289,3 +1289,56 @@ def temporal_loss_bwd(y, y_old, fwd, weight=1.0, g=None, grad=None, accumulate=F
                                       float(weight), _p(g), grad.data_ptr(), int(accumulate),
                                       _stream()), "stx_temporal_loss_bwd")
     return grad
+
+
+# ---------------------------------------------------------------------- colour control
+def _img3(t, name):
+    _req(t, name)
+    if t.dim() != 4 or t.shape[1] != 3:
+        raise N.NativeError(f"{name}: [n, 3, h, w] required (got {tuple(t.shape)})")
+    return t
+
+
+def _host_f32(v, count, name):
+    """A small host array (numpy / list / None) as a ctypes float array, or None."""
+    if v is None:
+        return None
+    flat = [float(e) for row in v for e in (row if hasattr(row, "__len__") else [row])]
+    if len(flat) != count:
+        raise ValueError(f"{name}: {count} values expected, got {len(flat)}")
+    return (C.c_float * count)(*flat)
+
+
+def color_stats(x, out=None):
+    """Per image of x [n, 3, h, w]: RGB mean[3] and the population covariance's upper
+    triangle [rr, rg, rb, gg, gb, bb], a device fp64 tensor [n, 9] (stx_color_stats)."""
+    _img3(x, "x")
+    n, _, h, w = x.shape
+    if out is None:
+        out = torch.empty((n, 9), device=x.device, dtype=torch.float64)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() \
+        and out.numel() == 9 * n, (out.shape, out.dtype)
+    L = lib()
+    wp, wn = _scratch().get(L.stx_color_stats_ws(n, h, w), x.device)
+    check(L.stx_color_stats(x.data_ptr(), out.data_ptr(), n, h, w, wp, wn, _stream()),
+          "stx_color_stats")
+    return out
+
+
+def color_affine(x, M, b=None, base=None, lo=None, hi=None, out=None):
+    """out[c] = clamp(base[c] + sum_d M[c][d] (x[d] - base[d]) + b[c]) per pixel of
+    [n, 3, h, w] (stx_color_affine).  M [3][3], b, lo, hi [3]: host values, baked into the
+    launch; base None reads as zeros; lo / hi None: no clamp.  out may be x or base."""
+    _img3(x, "x")
+    if out is None:
+        out = torch.empty_like(x)
+    for t, nm in ((base, "base"), (out, "out")):
+        if t is not None:
+            _img3(t, nm)
+            assert t.shape == x.shape, (nm, t.shape, x.shape)
+    n, _, h, w = x.shape
+    check(lib().stx_color_affine(x.data_ptr(), _p(base), out.data_ptr(), n, h, w,
+                                 _host_f32(M, 9, "M"), _host_f32(b, 3, "b"),
+                                 _host_f32(lo, 3, "lo"), _host_f32(hi, 3, "hi"), _stream()),
+          "stx_color_affine")
+    return out

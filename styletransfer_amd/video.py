@@ -23,7 +23,7 @@ from typing import Iterator
 import numpy as np
 import torch
 
-from . import constants, img_utils, ops
+from . import color, constants, img_utils, ops
 
 VIDEO_EXTS = (".mp4", ".avi", ".mov", ".mkv", ".gif", ".webm")
 FRAME_EXTS = (".png", ".jpg", ".jpeg", ".bmp")
@@ -91,10 +91,16 @@ class FrameEngine:
     also holds their conditioning (centre crop, Pillow-exact resize to the engine's
     size, normalisation: img_utils.FixedConditioner) written straight into the
     frame channels of the 6-channel input -- the per-frame path of
-    process_video (stransfer/network.py:1117-1131) with no host-side resize."""
+    process_video (stransfer/network.py:1117-1131) with no host-side resize.
 
-    def __init__(self, net, shape, device=None, graph=True, raw_hw=None):
+    preserve_color=True: `out` is the luminance merge of the stylised frame onto the
+    input frame (color.merge_luminance: the frame keeps its colours), one launch in the
+    place of the output copy.  `prev` still receives the un-merged network output, so
+    the recurrence -- every later frame's network input -- is what it is without it."""
+
+    def __init__(self, net, shape, device=None, graph=True, raw_hw=None, preserve_color=False):
         self.net = net
+        self.preserve_color = bool(preserve_color)
         self.dev = torch.device(device or constants.DEVICE)
         n, c, h, w = shape
         assert c == 3 and n == 1, shape  # the reference converts one video (batch 1)
@@ -124,7 +130,10 @@ class FrameEngine:
         # pass, [loss(w=1), ||y - y_prev||, ||x - x_prev||]
         ops.temporal_loss(y, self.prev, self.frame, self.prev_frame, 1.0,
                           out=self.scal[:3])
-        self.out.copy_(y)
+        if self.preserve_color:
+            color.merge_luminance(y, self.frame, out=self.out)
+        else:
+            self.out.copy_(y)
         self.prev.copy_(y)                 # next step's "old stylised" channels
         self.prev_frame.copy_(self.frame)
 
@@ -171,8 +180,9 @@ class FrameEngine:
 
 
 def process_video(net, video_path, style_name="nsp", working_dir="workdir/", out_dir="results/",
-                  fps=24.0, graph=True, max_frames=90 * 24) -> str:
-    """VideoTransformNet.process_video (stransfer/network.py:1071-1158) on FrameEngine."""
+                  fps=24.0, graph=True, max_frames=90 * 24, preserve_color=False) -> str:
+    """VideoTransformNet.process_video (stransfer/network.py:1071-1158) on FrameEngine.
+    preserve_color: every written frame keeps its input frame's colours."""
     working_dir = os.path.join(constants.PROJECT_ROOT_PATH, working_dir)
     out_dir = os.path.join(constants.PROJECT_ROOT_PATH, out_dir)
     import shutil
@@ -186,9 +196,9 @@ def process_video(net, video_path, style_name="nsp", working_dir="workdir/", out
         # run inside the per-frame graph (bit-identical to image_loader_transform)
         if eng is None or eng.cond.h != frame.shape[0] or eng.cond.w != frame.shape[1]:
             if eng is not None:  # a clip whose frame size changes: a new engine, as the
-                prev = eng.out.clone()  # reference, but keep the recurrence going
+                prev = eng.prev.clone()  # reference, but keep the recurrence going
             eng2 = FrameEngine(net, (1, 3, S, S), constants.DEVICE, graph=graph,
-                               raw_hw=frame.shape[:2])
+                               raw_hw=frame.shape[:2], preserve_color=preserve_color)
             if eng is not None:
                 eng2.prev.copy_(prev)
                 eng2.prev_frame.copy_(eng.prev_frame)
