@@ -695,6 +695,37 @@ int stx_image_condition(const void* src, const stx_image_meta* meta, int b, int 
                         const int* coef, int size, const float* mean, const float* std_,
                         float* out, void* tmp, size_t tmp_bytes, void* stream);
 
+/* fp32 separable resampling (scale control, Gatys et al. 2017 section 6: the pyramid levels
+ * of a coarse-to-fine transfer): [nc][hi][wi] planes to [nc][ho][wo], antialiased, half-pixel
+ * centres -- the semantics of torch.nn.functional.interpolate(mode = "bilinear" | "bicubic",
+ * align_corners = False, antialias = True).
+ *
+ * Per axis, scale = in / out, s = max(scale, 1), radius 1 (triangle) or 2 (cubic, Keys
+ * a = -0.5), support = radius s, and for output i the centre c = scale (i + 0.5):
+ *   first = max(0, int(c - support + 0.5)),  end = min(in, int(c + support + 0.5)),
+ *   w_j = f((j - c + 0.5) / s) for j in [first, end), divided by their sum
+ * (fp64, rounded to fp32 once).
+ *
+ * stx_resample_plan (HOST function, needs no GPU) fills first[out], count[out] and
+ * w[out][k] (zero padded) and returns the largest tap count, which k must be at least;
+ * with first = count = w = NULL it only returns that count.  On a bad argument it returns
+ * -STX_E_INVALID (a count can exceed any error code; the sign tells them apart).
+ *
+ * stx_resample2d: a horizontal pass into the workspace, then a vertical pass; the tables
+ * are DEVICE copies of a plan's arrays (x: wi -> wo, y: hi -> ho).  An axis whose size does
+ * not change is skipped and its tables may be NULL; an identity resize is an exact copy.
+ * Each output is an fmaf chain over its taps in ascending order from w0 x0: bit-reproducible
+ * and independent of nc.  y must not overlap x.  nc <= 65535, every side <= 4096. */
+#define STX_FILTER_TRIANGLE 0
+#define STX_FILTER_CUBIC 1
+int stx_resample_plan(int in_size, int out_size, int filter, int* first, int* count, float* w,
+                      int k);
+size_t stx_resample2d_ws(int nc, int hi, int wi, int ho, int wo);
+int stx_resample2d(const float* x, float* y, int nc, int hi, int wi, int ho, int wo,
+                   const int* xfirst, const int* xcount, const float* xw, int xk,
+                   const int* yfirst, const int* ycount, const float* yw, int yk, void* ws,
+                   size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -207,6 +207,10 @@ SIGNATURES = {
     "stx_tv_loss": (i32, [vp, vp, vp, f32, vp, i32, i32, i32, i32, f32, vp, sz, vp]),
     "stx_resample_coeffs": (i32, [i32, i32, vp, vp, i32]),
     "stx_image_condition": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "stx_resample_plan": (i32, [i32, i32, i32, vp, vp, vp, i32]),
+    "stx_resample2d_ws": (sz, [i32, i32, i32, i32, i32]),
+    "stx_resample2d": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32,
+                             vp, sz, vp]),
     "stx_temporal_loss_ws": (sz, []),
     "stx_temporal_loss": (i32, [vp, vp, vp, vp, i64, f32, vp, vp, sz, vp]),
     "stx_temporal_loss_bwd": (i32, [vp, vp, i64, vp, f32, vp, vp, i32, vp]),

@@ -8,6 +8,7 @@ import torch
 from PIL import Image
 
 from .. import c_logging, constants, img_utils, network
+from .gatys_st import level_steps, parse_scale_steps, parse_scales
 
 LOGGER = c_logging.get_logger()
 MAX_REGIONS = 4  # STX_GUIDE_MAX (include/stx.h)
@@ -50,17 +51,25 @@ def mask_loader(path: str, imsize=None) -> torch.Tensor:
               help="Keep the content image's colours: match = recolour every region's style "
                    "image to the whole content image's mean and covariance first; luminance "
                    "= transfer on luminance only, then restore the content's chroma")
+@click.option("--scales", callback=parse_scales, default=None, metavar="S0,S1,...",
+              help="Coarse to fine: transfer at S0, resample the result up and continue at S1, "
+                   "... (ascending multiples of 4); images and masks are loaded at the largest")
+@click.option("--scale-steps", callback=parse_scale_steps, default=None, metavar="N0,N1,...",
+              help="Iterations per --scales level (default: -s at every level)")
 def gatys_guided(content_image_path, regions, out_name, steps, content_weight, style_weight,
-                 preserve_color):
+                 preserve_color, scales, scale_steps):
     """Gatys style transfer with one style per masked region of the image."""
     if len(regions) > MAX_REGIONS:
         raise click.UsageError(f"at most {MAX_REGIONS} regions (-r), got {len(regions)}")
     specs = [parse_region(r) for r in regions]
+    steps = level_steps(scales, scale_steps, steps)
+    top = None if scales is None else scales[-1]
     root = constants.PROJECT_ROOT_PATH
-    content_image = img_utils.image_loader(os.path.join(root, content_image_path))
-    style_images = [img_utils.image_loader(os.path.join(root, s)) for s, _, _ in specs]
-    guides = [mask_loader(os.path.join(root, m)) for _, m, _ in specs]
-    style_guides = [None if sm is None else mask_loader(os.path.join(root, sm))
+    content_image = img_utils.image_loader(os.path.join(root, content_image_path), imsize=top)
+    style_images = [img_utils.image_loader(os.path.join(root, s), imsize=top)
+                    for s, _, _ in specs]
+    guides = [mask_loader(os.path.join(root, m), top) for _, m, _ in specs]
+    style_guides = [None if sm is None else mask_loader(os.path.join(root, sm), top)
                     for _, _, sm in specs]
     if all(g is None for g in style_guides):
         style_guides = None
@@ -72,7 +81,8 @@ def gatys_guided(content_image_path, regions, out_name, steps, content_weight, s
     net = network.StyleNetwork(style_images[0], content_image)
     converted = net.train_gatys_guided(style_images, content_image, guides,
                                        style_guides=style_guides, style_weight=style_weight,
-                                       content_weight=content_weight, steps=steps)
+                                       content_weight=content_weight, steps=steps,
+                                       **({} if scales is None else dict(sizes=scales)))
     if finish is not None:
         converted = finish(converted)
     out_dir = os.path.join(root, "results")

@@ -347,8 +347,11 @@ class StyleNetwork(nn.Module):
         return optt([input_img.requires_grad_()])
 
     def train_gatys(self, style_image: torch.Tensor, content_image: torch.Tensor, steps=550,
-                    style_weight=100_000, content_weight=1) -> torch.Tensor:
-        """L-BFGS Gatys optimisation from the content image (stransfer/network.py:411-458)."""
+                    style_weight=100_000, content_weight=1,
+                    style_layer_weights=None) -> torch.Tensor:
+        """L-BFGS Gatys optimisation from the content image (stransfer/network.py:411-458).
+        style_layer_weights: five non-negative multipliers of style_weight, one per style
+        tap (the fused engine only)."""
         assert isinstance(style_image, torch.Tensor), "Images need to be already loaded"
         assert isinstance(content_image, torch.Tensor), "Images need to be already loaded"
         content_image = _dev(content_image)
@@ -356,14 +359,19 @@ class StyleNetwork(nn.Module):
             # the fused loss engine: direction, closure and gradient statistics replayed
             # as one hipGraph per L-BFGS iteration (vgg.GatysLBFGS), torch's control flow
             targets = [l.target for l, _ in self.style_losses]
+            kw = {} if style_layer_weights is None else \
+                dict(style_layer_weights=style_layer_weights)
             eng = V.GatysLBFGS(self.features(), None, content_image.contiguous(),
-                               style_weight, content_weight, targets=targets)
+                               style_weight, content_weight, targets=targets, **kw)
 
             def log(loss):  # a host float from the iteration's one read: no extra sync
                 LOGGER.info("Loss: %s", loss)  # stransfer/network.py:453 logs at INFO
             for _ in tqdm(range(steps)):
                 eng.step(on_eval=log)
             return eng.x.requires_grad_()
+        if style_layer_weights is not None:
+            raise ValueError("style_layer_weights needs the fused engine (the standard tap "
+                             "layout on the GPU)")
         image = content_image.clone()
         opt = self.get_content_optimizer(image, optt=optim.LBFGS)  # -> the HIP L-BFGS
 
@@ -382,29 +390,52 @@ class StyleNetwork(nn.Module):
         return image
 
     def train_gatys_adam(self, style_image, content_image, steps=500, style_weight=100_000,
-                         content_weight=1, graph=True) -> torch.Tensor:
+                         content_weight=1, graph=True, style_layer_weights=None) -> torch.Tensor:
         """The Adam variant of the Gatys loop (get_content_optimizer's default
-        optimiser; BASELINE.json's "Adam iters"): one hipGraph replay per iteration."""
+        optimiser; BASELINE.json's "Adam iters"): one hipGraph replay per iteration.
+        style_layer_weights: five non-negative multipliers of style_weight, one per tap."""
         assert isinstance(style_image, torch.Tensor), "Images need to be already loaded"
         targets = [l.target for l, _ in self.style_losses]  # set in __init__, as the reference
+        kw = {} if style_layer_weights is None else dict(style_layer_weights=style_layer_weights)
         eng = V.GatysEngine(self.features(), None, _dev(content_image), style_weight,
-                            content_weight, targets=targets)
+                            content_weight, targets=targets, **kw)
         eng.run(steps, graph=graph)
         return eng.x
 
     def train_gatys_guided(self, style_images, content_image, guides, style_guides=None,
                            region_weights=None, steps=500, style_weight=100_000,
-                           content_weight=1, graph=True) -> torch.Tensor:
+                           content_weight=1, graph=True, sizes=None) -> torch.Tensor:
         """Region-guided Gatys optimisation (Adam, one hipGraph replay per iteration):
         region r of the canvas (guides[r], an HxW map in [0, 1]) takes the style of
         style_images[r], optionally only of the part style_guides[r] selects; pixels no
-        guide covers get the content loss only (vgg.GuidedGatysEngine)."""
+        guide covers get the content loss only (vgg.GuidedGatysEngine).  sizes: coarse to
+        fine over these sides (scale.coarse_to_fine_guided; steps: an int or one count per
+        level), images and guides given at the largest."""
+        if sizes is not None:
+            from . import scale
+            return scale.coarse_to_fine_guided(
+                self.features(), style_images, content_image, guides, sizes, steps,
+                style_guides=style_guides, region_weights=region_weights,
+                style_weight=style_weight, content_weight=content_weight)
         eng = V.GuidedGatysEngine(self.features(), [_dev(s) for s in style_images],
                                   _dev(content_image), guides, style_guides=style_guides,
                                   region_weights=region_weights, style_weight=style_weight,
                                   content_weight=content_weight)
         eng.run(steps, graph=graph)
         return eng.x
+
+    def train_gatys_multiscale(self, style_image, content_image, sizes, steps,
+                               optimizer="lbfgs", style_weight=100_000, content_weight=1,
+                               style_layer_weights=None) -> torch.Tensor:
+        """Coarse-to-fine Gatys optimisation (scale.coarse_to_fine; Gatys et al. 2017,
+        section 6.2): the images are given at sizes[-1]; every level takes its own style
+        targets from style_image at that level's size.  steps: an int (every level) or one
+        count per level; for "lbfgs" outer steps, as train_gatys counts them."""
+        from . import scale
+        kw = {} if style_layer_weights is None else dict(style_layer_weights=style_layer_weights)
+        return scale.coarse_to_fine(self.features(), style_image, content_image, sizes, steps,
+                                    optimizer=optimizer, style_weight=style_weight,
+                                    content_weight=content_weight, **kw)
 
 
 # ============================================================== ImageTransformNet

@@ -22,7 +22,8 @@ __all__ = [
     "bias_grad", "gram", "style_loss", "gram_bwd", "guided_style_loss", "guided_gram_bwd", "mse", "diff_scale", "loss_combine",
     "maxpool2x2", "maxpool2x2_bwd", "relupool_bwd", "relu", "relu_bwd", "adam_step",
     "instnorm_fwd", "instnorm_bwd", "cin_mix", "upsample2x", "upsample2x_bwd", "tv_loss",
-    "temporal_loss", "temporal_loss_bwd", "color_stats", "color_affine",
+    "temporal_loss", "temporal_loss_bwd", "color_stats", "color_affine", "resample_plan",
+    "resample2d",
 ]
 
 
@@ -1341,4 +1342,70 @@ def color_affine(x, M, b=None, base=None, lo=None, hi=None, out=None):
                                  _host_f32(M, 9, "M"), _host_f32(b, 3, "b"),
                                  _host_f32(lo, 3, "lo"), _host_f32(hi, 3, "hi"), _stream()),
           "stx_color_affine")
+    return out
+
+
+# ------------------------------------------------------------------------ scale control
+FILTERS = {"triangle": 0, "cubic": 1}  # STX_FILTER_* (include/stx.h)
+_RESAMPLE_TABLES = {}  # (in, out, filter, device) -> (first, count, w, k) on the device
+
+
+def resample_plan(n_in, n_out, filter="cubic"):
+    """(first [out] int32, count [out] int32, w [out][k] fp32, k) of one axis, numpy arrays
+    (stx_resample_plan: a host function, no GPU needed)."""
+    import numpy as np
+    if filter not in FILTERS:
+        raise ValueError(f"filter {filter!r}: expected one of {tuple(FILTERS)}")
+    L = lib()
+    k = L.stx_resample_plan(int(n_in), int(n_out), FILTERS[filter], None, None, None, 0)
+    if k <= 0:
+        check(-k, "stx_resample_plan")
+    first = np.zeros(n_out, np.int32)
+    count = np.zeros(n_out, np.int32)
+    w = np.zeros((n_out, k), np.float32)
+    rc = L.stx_resample_plan(int(n_in), int(n_out), FILTERS[filter], first.ctypes.data,
+                             count.ctypes.data, w.ctypes.data, k)
+    if rc != k:
+        check(-rc if rc < 0 else 1001, "stx_resample_plan")  # (1001: STX_E_INVALID)
+    return first, count, w, k
+
+
+def _resample_tables(n_in, n_out, filter, device):
+    """The device copy of an axis plan, uploaded once per (in, out, filter, device): a
+    later call with the same sizes makes no host-to-device copy (and can be captured)."""
+    key = (int(n_in), int(n_out), filter, torch.device(device))
+    t = _RESAMPLE_TABLES.get(key)
+    if t is None:
+        first, count, w, k = resample_plan(n_in, n_out, filter)
+        t = (torch.from_numpy(first).to(device), torch.from_numpy(count).to(device),
+             torch.from_numpy(w).to(device), k)
+        _RESAMPLE_TABLES[key] = t
+    return t
+
+
+def resample2d(x, size, filter="cubic", out=None):
+    """x [n, c, h, w] or [r, h, w] resized to size = (ho, wo) (an int: both), antialiased,
+    half-pixel centres (stx_resample2d; torch's interpolate(..., align_corners=False,
+    antialias=True) with "bilinear" for "triangle" and "bicubic" for "cubic").  out must
+    not alias x; an unchanged size gives an exact copy."""
+    _req(x, "x")
+    if x.dim() not in (3, 4):
+        raise N.NativeError(f"x: [n, c, h, w] or [r, h, w] required (got {tuple(x.shape)})")
+    ho, wo = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    lead, (hi, wi) = tuple(x.shape[:-2]), x.shape[-2:]
+    nc = 1
+    for d in lead:
+        nc *= d
+    if out is None:
+        out = torch.empty(lead + (ho, wo), device=x.device, dtype=torch.float32)
+    _req(out, "out")
+    assert tuple(out.shape) == lead + (ho, wo), (out.shape, lead, ho, wo)
+    none = (None, None, None, 0)
+    xf, xc, xw, xk = _resample_tables(wi, wo, filter, x.device) if wi != wo else none
+    yf, yc, yw, yk = _resample_tables(hi, ho, filter, x.device) if hi != ho else none
+    L = lib()
+    wp, wn = _scratch().get(L.stx_resample2d_ws(nc, hi, wi, ho, wo), x.device)
+    check(L.stx_resample2d(x.data_ptr(), out.data_ptr(), nc, hi, wi, ho, wo, _p(xf), _p(xc),
+                           _p(xw), xk, _p(yf), _p(yc), _p(yw), yk, wp, wn, _stream()),
+          "stx_resample2d")
     return out

@@ -213,6 +213,33 @@ class LossState:
     mse_parts: torch.Tensor = None              # content tap's fused MSE sums (2 per tile)
 
 
+def tap_weights(style_weight, layer_weights=None):
+    """The five per-tap style weights: a float style_weight for every tap (exactly
+    [style_weight] * 5 when layer_weights is None), or style_weight times five non-negative
+    multipliers; a sequence of five floats passes through (loss_forward's folded_weights)."""
+    if not isinstance(style_weight, (int, float)):
+        if layer_weights is not None:
+            raise ValueError("style_weight per tap and layer_weights: give one of them")
+        sws = [float(v) for v in style_weight]
+        if len(sws) != 5:
+            raise ValueError(f"style weights: one float or five, got {len(sws)}")
+        return sws
+    if layer_weights is None:
+        return [float(style_weight)] * 5
+    lw = [float(v) for v in layer_weights]
+    if len(lw) != 5 or min(lw) < 0 or not all(np.isfinite(lw)):
+        raise ValueError(f"style_layer_weights: five non-negative numbers expected, got {lw}")
+    return [float(style_weight) * v for v in lw]
+
+
+def _folded_style(style_weight, layer_weights):
+    """The style half of an engine's folded_weights: the plain float without per-tap
+    multipliers (the call is then today's, argument for argument), else the five."""
+    if layer_weights is None:
+        return float(style_weight)
+    return tap_weights(float(style_weight), layer_weights)
+
+
 def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
                  folded_weights=None, total=None, extra_slot=False):
     """Forward of all 7 losses for input batch x [B,3,H,W] given style targets and
@@ -221,8 +248,11 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
     folded_weights=(style_weight, content_weight): constant loss weights are baked
     into the backward operators (A_l scaled by style_weight; the content term's
     alpha*Z4 on A_4's diagonal) so the backward needs no device scalars — the
-    Gatys engine's case.  None: operators for weight 1; the backward scales by the
-    upstream gradient vector (autograd case).
+    Gatys engine's case.  style_weight: one float, or five (one per tap, section 6.1 of
+    Gatys et al. 2017: a zero drops that tap -- its operator A and max|A| are zero, and
+    the split phases scale by a power of two taken from max|A|'s exponent, never by a
+    quotient, so a zero contributes zero).  None: operators for weight 1; the backward
+    scales by the upstream gradient vector (autograd case).
 
     The five style-loss reductions are deferred (partials kept in per-layer
     workspaces) and done in one launch after the forward, together with the
@@ -245,10 +275,10 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
     B, _, H, W = x.shape
     z4_shape = (B, 128, H // 2, W // 2)
     assert tuple(c4.shape) == z4_shape, (c4.shape, z4_shape)
-    sw, alpha = 1.0, 0.0
+    sws, alpha = [1.0] * 5, 0.0
     st.folded = folded_weights is not None
     if st.folded:
-        sw = float(folded_weights[0])
+        sws = tap_weights(folded_weights[0])
         alpha = float(folded_weights[1]) * 2.0 / (B * 128 * (H // 2) * (W // 2))
     st.alpha = alpha
     st.c4 = c4
@@ -285,7 +315,7 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
     def tap_loss(i, l, z, b_, c_, fuse_mse):
         if fuse_mse:  # style loss + content/feature/feature-mse in one pass over z
             st.parts[i], st.coef[i] = ops.style_content_loss(
-                z, targets[i], c4, st.losses[5:8], weight=sw, diag_alpha=alpha,
+                z, targets[i], c4, st.losses[5:8], weight=sws[i], diag_alpha=alpha,
                 coef=st.coef[i], z_amax=slot(st.amax, l + 1), defer_ws=st.lws[i], fin=fin)
             return
         fused_mse = False
@@ -297,13 +327,13 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
             fused_mse = l == CONTENT_CONV and content is not None
             st.parts[i], st.coef[i] = ops.style_loss_from_parts(
                 gp, gp.numel() // (b_ * ops.gram_tile_units(c_) * 4096), b_, c_, z[0, 0].numel(),
-                targets[i], weight=sw, diag_alpha=alpha if l == CONTENT_CONV else 0.0,
+                targets[i], weight=sws[i], diag_alpha=alpha if l == CONTENT_CONV else 0.0,
                 coef=st.coef[i], defer_ws=st.lws[i], fin=fin,
                 mse_parts=st.mse_parts if fused_mse else None,
                 mse_out=st.losses[5:8] if fused_mse else None)
         else:
             st.parts[i], st.coef[i] = ops.style_loss(
-                z, targets[i], weight=sw, diag_alpha=alpha if l == CONTENT_CONV else 0.0,
+                z, targets[i], weight=sws[i], diag_alpha=alpha if l == CONTENT_CONV else 0.0,
                 coef=st.coef[i], z_amax=slot(st.amax, l + 1) if split else None,
                 defer_ws=st.lws[i], fin=fin)
         if l == CONTENT_CONV and not fused_mse:  # content, feature, feature-mse: one pass
@@ -339,7 +369,7 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
     extra = None
     if total is not None:
         fw = folded_weights if folded_weights is not None else (1.0, 1.0)
-        w = [float(fw[0])] * 5 + [float(fw[1])]
+        w = tap_weights(fw[0]) + [float(fw[1])]
         extra = st.losses[5:6]
         if extra_slot:  # st.losses[8] (written by the caller, e.g. TV) joins the total
             w += [0.0, 0.0, 1.0]
@@ -492,7 +522,7 @@ class GatysEngine:
 
     def __init__(self, feat: VGGFeatures, style_image, content_image, style_weight=100_000,
                  content_weight=1, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, init=None,
-                 targets=None):
+                 targets=None, style_layer_weights=None):
         dev = feat.device
         self.feat = feat
         if targets is None:
@@ -508,8 +538,10 @@ class GatysEngine:
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.adam_ws = torch.zeros(16, dtype=torch.float32, device=dev)
         self.lr, self.betas, self.eps = lr, betas, eps
-        self.sw, self.cw = float(style_weight), float(content_weight)
-        self.g = torch.tensor([self.sw] * 5 + [self.cw, 0.0], device=dev, dtype=torch.float32)
+        # style_layer_weights: five non-negative multipliers of style_weight, one per tap
+        self.sw, self.cw = _folded_style(style_weight, style_layer_weights), float(content_weight)
+        self.g = torch.tensor(tap_weights(self.sw) + [self.cw, 0.0], device=dev,
+                              dtype=torch.float32)
         self.total = torch.zeros((), device=dev, dtype=torch.float32)
         self.st = LossState()
         self.scratch = {}
@@ -584,7 +616,8 @@ class GatysLBFGS:
     discarded."""
 
     def __init__(self, feat: VGGFeatures, style_image, content_image, style_weight=100_000,
-                 content_weight=1, targets=None, init=None, **lbfgs_kw):
+                 content_weight=1, targets=None, init=None, style_layer_weights=None,
+                 **lbfgs_kw):
         from .optim import LBFGS
         dev = feat.device
         self.feat = feat
@@ -596,7 +629,7 @@ class GatysLBFGS:
         src = self.content if init is None else init.to(dev, torch.float32)
         self.x = src.clone().contiguous()
         self.grad = torch.zeros_like(self.x)
-        self.sw, self.cw = float(style_weight), float(content_weight)
+        self.sw, self.cw = _folded_style(style_weight, style_layer_weights), float(content_weight)
         self.total = torch.zeros((), device=dev, dtype=torch.float32)
         self.st = LossState()
         self.scratch = {}
