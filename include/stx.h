@@ -48,6 +48,19 @@ extern "C" {
 #define STX_IN_RELU_POOL2 2 /* v = maxpool2x2(max(x,0))   (VGG ReLU + MaxPool2d) */
 #define STX_IN_UPSAMPLE2 3  /* v = x[y/2][x/2]            (nn.Upsample nearest x2) */
 #define STX_IN_DILATE2 4    /* v = x[y/2][x/2] at even y,x else 0 (stride-2 dgrad) */
+/* A NaN in x under STX_IN_RELU / STX_IN_RELU_POOL2 (a NaN that reaches the GEMM makes every
+ * output it touches NaN; one the loader's ReLU removes reads as 0, or in a pool window as
+ * if it were absent), one line per loader:
+ *   conv.hip (fp32 MFMA, every loader form)     fmaxf: NaN reads as 0
+ *   wgrad.hip (fp32 weight gradient)            fmaxf: NaN reads as 0
+ *   conv16.hip (fp16 hi/lo split)               integer max of the bit pattern: a NaN with
+ *                                               the sign bit clear is kept (and wins its
+ *                                               pool window), one with it set reads as 0
+ *   convfew.hip, conv9.hip (few-channel / 9x9)  as conv16.hip
+ *   wgrad16.hip                                 wgrad16_kernel as conv16.hip;
+ *                                               wgrad16_lds_kernel fmaxf: NaN reads as 0
+ * The split kernels also scale by in_amax, which a NaN input makes NaN (stx_amax).  The
+ * stand-alone stx_relu_fwd / stx_maxpool2x2_fwd and the fused pool_out keep every NaN. */
 
 typedef struct stx_conv_params {
   const float* x;     /* physical input [n][cin][h][w] */
@@ -418,7 +431,9 @@ int stx_color_affine(const float* x, const float* base, float* out, int n, int h
  *   mode 2: both from one pass (16-B aligned a, b; relu_inputs ignored):
  *           out[0] = mean((a-b)^2), out[1] = mean((relu a - relu b)^2)^2 / n,
  *           out[2] = mean((relu a - relu b)^2)   (content + feature at conv2_2)
- * grad (optional, mode 0): grad = gscale * 2*(a-b)/n. */
+ * grad (optional, mode 0): grad = gscale * 2*(a-b)/n.
+ * A NaN in a or b makes the plain sums NaN; the relu'd sums (relu_inputs, mode 2's
+ * out[1] / out[2]) read it as 0 (fmaxf), as the fp32 conv loaders above do. */
 size_t stx_mse_ws(long long n);
 int stx_mse(const float* a, const float* b, long long n, int relu_inputs, int mode,
             float* out, float* grad, float gscale, void* ws, size_t ws_bytes, void* stream);
@@ -543,21 +558,28 @@ int stx_lbfgs_grad_stats(const float* g, long long n, const float* loss, float* 
                          int clear_n, void* ws, size_t ws_bytes, void* stream);
 
 /* MaxPool2d(2,2) on (optionally relu'd) input; idx = flat y*w+x argmax per plane,
- * torch CPU semantics (first max in row-major window order; NaN propagates). idx may be NULL. */
+ * torch CPU semantics (first max in row-major window order; NaN propagates, with
+ * relu_input too: the ReLU keeps a NaN, as torch's, and idx points at the window's last
+ * NaN). idx may be NULL.  Floor mode: an odd trailing row / column is never pooled. */
 int stx_maxpool2x2_fwd(const float* x, float* y, long long* idx, int nc, int h, int w,
                        int relu_input, void* stream);
 /* dx = scatter(dy at idx)  (dx fully written, gather form) */
 int stx_maxpool2x2_bwd(const float* dy, const long long* idx, float* dx, int nc, int h, int w,
                        void* stream);
 /* dz = unpool(dp) * (z > 0): backward of ReLU + MaxPool2d(2,2) with the argmax
- * recomputed from z (dz fully written; z is the pre-ReLU tensor [nc][h][w]) */
+ * recomputed from z (dz fully written; z is the pre-ReLU tensor [nc][h][w]).  A NaN z
+ * is not positive: dz = 0 there, as torch's backward gives (the argmax search ranks it
+ * as 0). */
 int stx_relupool_bwd(const float* dp, const float* z, float* dz, int nc, int h, int w,
                      void* stream);
+/* y = x <= 0 ? +0 : x -- a NaN stays NaN, as torch.relu keeps it */
 int stx_relu_fwd(const float* x, float* y, long long n, void* stream);
-/* dx = dy * (y > 0) */
+/* dx = dy * (y > 0): 0 at a NaN y, as torch's threshold backward */
 int stx_relu_bwd(const float* dy, const float* y, float* dx, long long n, void* stream);
 
-/* Adam (torch.optim.Adam semantics, in place; 16-byte aligned buffers).
+/* Adam (torch.optim.Adam semantics, in place).  Any 4-byte aligned buffers are accepted:
+ * with p, g, m and v all 16-byte aligned the kernel moves 16 bytes per access, otherwise
+ * one float (the two forms agree to rounding, not bit for bit).
  * step_dev: device int32 step counter, incremented on the device by every call so
  * a captured graph replays correctly.  ws: stx_adam_ws() bytes of device scratch. */
 size_t stx_adam_ws(void);

@@ -1603,8 +1603,7 @@ __global__ void amax_kernel(const float* __restrict__ x, long long n, float* __r
   const long long stride = (long long)gridDim.x * blockDim.x;
   const long long t0 = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   auto upd = [&](float v) {
-    const float a = fabsf(v);
-    m = (a != a) ? a : fmaxf(m, a);
+    m = max_nan_wins(m, fabsf(v));
   };
   for (long long i = t0; i < n4; i += stride) {
     const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
@@ -1627,8 +1626,7 @@ __device__ __forceinline__ void amax_slot_body(const float* __restrict__ x, long
   const long long b0 = slot * per, b1 = min(n4, b0 + per);
   float m = 0.f;
   auto upd = [&](float v) {
-    const float a = fabsf(v);
-    m = (a != a) ? a : fmaxf(m, a);
+    m = max_nan_wins(m, fabsf(v));
   };
 #pragma unroll 4
   for (long long i = b0 + threadIdx.x; i < b1; i += 1024) {
@@ -1642,15 +1640,14 @@ __device__ __forceinline__ void amax_slot_body(const float* __restrict__ x, long
     for (long long i = 4 * n4 + threadIdx.x; i < n; i += 1024) upd(x[i]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    const float other = __shfl_xor(m, o, 64);
-    m = (other != other) ? other : fmaxf(m, other);
+    m = max_nan_wins(m, __shfl_xor(m, o, 64));
   }
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
     float r = red[0];
 #pragma unroll
-    for (int i = 1; i < 16; ++i) r = (red[i] != red[i]) ? red[i] : fmaxf(r, red[i]);
+    for (int i = 1; i < 16; ++i) r = max_nan_wins(r, red[i]);
     out[slot] = r;
   }
 }

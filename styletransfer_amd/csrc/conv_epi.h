@@ -58,20 +58,24 @@ __device__ __forceinline__ void atomic_max_abs(float* slot, float m) {
 // ~12-15 ns each chip-wide (8192 of them stalled a 64 MB pass for 100 us; 1024 at a
 // conv's tail cost ~15 us)
 // nwaves: the waves taking part (0: the whole block; a K2 block's epilogue runs on 4)
+// max of two values in which a NaN on EITHER side wins: fmaxf(NaN, x) is x, so testing
+// only the incoming operand loses a NaN already held (in a butterfly it merely swaps
+// lanes and reaches lane 0 from lane 63 alone)
+__device__ __forceinline__ float max_nan_wins(float m, float other) {
+  return (other != other) ? other : (m != m) ? m : fmaxf(m, other);
+}
+
 __device__ __forceinline__ void block_max_to(float* group, float m, int nwaves = 0) {
   __shared__ float red[16];  // up to 1024-thread blocks
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float other = __shfl_xor(m, o, 64);
-    m = (other != other) ? other : fmaxf(m, other);
-  }
+  for (int o = 32; o > 0; o >>= 1) m = max_nan_wins(m, __shfl_xor(m, o, 64));
   const int tid = threadIdx.x;
   if ((tid & 63) == 0) red[tid >> 6] = m;
   lds_sync();  // (not a __syncthreads: the caller's output stores need not drain first)
   if (tid == 0) {
     float r = red[0];
     const int nw = nwaves > 0 ? nwaves : (int)(blockDim.x >> 6);
-    for (int i = 1; i < nw; ++i) r = (red[i] != red[i]) ? red[i] : fmaxf(r, red[i]);
+    for (int i = 1; i < nw; ++i) r = max_nan_wins(r, red[i]);
     const int bid = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     atomic_max_abs(group + (bid & (STX_AMAX_SLOTS - 1)), fabsf(r));
   }

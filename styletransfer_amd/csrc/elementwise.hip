@@ -133,6 +133,10 @@ __global__ void diff_scale_kernel(const float* __restrict__ a, const float* __re
 }
 
 // ------------------------------------------------------------------ pooling
+// ReLU as torch's: a NaN stays NaN (fmaxf(NaN, 0) is 0, which would heal a diverged
+// tensor here and not in the fused pool_out epilogue, conv_epi.h); -0 gives +0.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v <= 0.f ? 0.f : v; }
+
 // MaxPool2d(2,2) (VGG pieces, stransfer/network.py:264-275); torch CPU kernel
 // semantics: scan the window row-major, update when (v > max) || isnan(v).
 __global__ void maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
@@ -154,7 +158,7 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ x, float* __restric
       for (int dx = 0; dx < 2; ++dx) {
         const int yy = 2 * oy + dy, xx = 2 * ox + dx;
         float v = src[yy * w + xx];
-        if (relu) v = fmaxf(v, 0.f);
+        if (relu) v = relu_keep_nan(v);
         if (v > best || isnan(v)) {
           best = v;
           bi = yy * w + xx;
@@ -220,7 +224,7 @@ __global__ void relupool_bwd_kernel(const float* __restrict__ dp, const float* _
 __global__ void relu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, long long n) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x)
-    y[i] = fmaxf(x[i], 0.f);
+    y[i] = relu_keep_nan(x[i]);
 }
 
 __global__ void relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y,
