@@ -128,7 +128,7 @@ typedef struct stx_conv_params {
    * of y y^T (fp32, fp16 hi/lo MFMA with a block-local power-of-two scale) as U 64 x 64
    * tiles: tile u to gram_part + ((n * U + u) * T + t) * 4096, T = stx_conv_gram_tiles(p),
    * U = 1 (cout 64) or 3 (cout 128: tiles (0,0), (0,1), (1,1) of the 128 x 128 matrix,
-   * diagonal tiles whole); stx_style_loss_from_parts reduces them. */
+   * diagonal tiles whole); stx_style_loss (parts) reduces them. */
   float* gram_part;
   /* with pool_out: pool_out = the 2x2 SUM of the output (no ReLU) and y is not written
    * -- the backward of nearest x2 upsampling (torch.nn.Upsample(scale_factor=2), the
@@ -142,7 +142,7 @@ typedef struct stx_conv_params {
    * partials of tiles g*STX_GRAM_GROUP .. g*STX_GRAM_GROUP+7 of image n form group g;
    * the last block of a group to finish sums the group's partials in tile order and
    * writes that sum to gram_part + (n_total * T + n * NG + g) * 4096 (NG =
-   * stx_conv_gram_groups(p)), so stx_style_loss_from_parts reads NG sums per image
+   * stx_conv_gram_groups(p)), so stx_style_loss (parts) reads NG sums per image
    * instead of T partials.  The per-tile slots then hold three of the four 32 x 32
    * blocks only (scratch); the gram_part slab needs (T + NG) * 4096 floats per image. */
   unsigned int* gram_cnt;
@@ -155,7 +155,7 @@ typedef struct stx_conv_params {
    * stransfer/network.py:134-201): the content target ref [n][cout][ho][wo]; block t of
    * image n then also writes sum (y - ref)^2 and sum (relu y - relu ref)^2 over its
    * outputs to mse_parts[2 (n T + t) + 0 / 1] (n * T * 2 floats), which
-   * stx_style_content_loss_from_parts reduces into the content / feature losses. */
+   * stx_style_loss (mse_parts) reduces into the content / feature losses. */
   const float* mse_ref;
   float* mse_parts;
   /* optional with in_mode STX_IN_UPSAMPLE2 on the split path (wt16 / w_amax of the same
@@ -184,17 +184,18 @@ typedef struct stx_conv_params {
 int stx_version(void);
 /* sizeof and the offset of the last member of each ABI struct, in this order:
  * stx_conv_params, stx_wprep_job, stx_loss_parts, stx_gram_fin_job, stx_in_pgrad_job,
- * stx_image_meta -- 12 values, min(n, 12) written to out; returns 12.  Bindings check
- * their struct mirrors against it. */
+ * stx_image_meta, stx_cin_job, stx_style_loss_params -- two values each, min(n, count)
+ * written to out; returns the count.  Bindings check their struct mirrors against it. */
 int stx_abi_layout(long long* out, int n);
 const char* stx_last_error_string(void);
 /* The ABI revision of this header (STX_ABI_VERSION): a host binding refuses a library of
  * another revision rather than pass arguments whose meaning changed (round 6:
  * stx_instnorm_bwd's second argument is beta, not y; 7: stx_conv_params.unpool_out;
- * 9: the guided Gram entry points).  The revision moves only when an existing entry
- * point or struct changes meaning; entry points that are merely added (the colour
- * control pair below) do not bump it -- a binding finds a missing symbol at load. */
-#define STX_ABI_VERSION 9
+ * 9: the guided Gram entry points; 10: stx_style_loss takes stx_style_loss_params).  The
+ * revision moves only when an existing entry point or struct changes meaning; entry
+ * points that are merely added (the colour control pair below) do not bump it -- a
+ * binding finds a missing symbol at load. */
+#define STX_ABI_VERSION 10
 int stx_abi_version(void);
 
 /* Padded GEMM dims the conv kernels expect for a (cin, cout, ks) conv. */
@@ -332,7 +333,7 @@ size_t stx_gram_ws(int b, int c, int hw);
 int stx_gram(const float* z, float* g, int b, int c, int hw, float scale,
              const float* z_amax, void* ws, size_t ws_bytes, void* stream);
 
-/* Style loss forward + backward coefficients (StyleLoss.forward):
+/* Style loss forward + backward coefficients (StyleLoss.forward; stx_style_loss below):
  *   G = gram(z)/(c*hw);  loss = mean((G - T)^2) over b*c*c  -> *loss (device scalar)
  *   A[b] = weight*4/(b*c*c*c*hw) * (G[b]-T) + diag_alpha*I     (A is [b][cpad][cpad])
  * so that dz = A·z (+ aux) is d(weight*loss)/dz; g_out (optional) receives G.
@@ -354,10 +355,6 @@ typedef struct stx_loss_parts {
 } stx_loss_parts;
 int stx_loss_finalize(const stx_loss_parts* lp, float* losses, const float* extra, int m,
                       const float* w_host, float* total, void* stream);
-int stx_style_loss(const float* z, const float* target, float* g_out, float* coef,
-                   float* loss, int b, int c, int hw, int target_batched, float weight,
-                   float diag_alpha, const float* z_amax, void* ws, size_t ws_bytes,
-                   void* stream);
 /* dz (+)= s * A[b]·z[b] (+ aux_scale*aux) — Gram backward as a 1x1 MFMA conv with
  * per-image weights; z viewed [b][c][h][w]; s = *acc_scale_dev (or 1 if NULL) */
 int stx_gram_bwd(const float* coef, const float* z, float* dz, int b, int c, int h, int w,
@@ -441,40 +438,12 @@ int stx_mse(const float* a, const float* b, long long n, int relu_inputs, int mo
 int stx_diff_scale(const float* a, const float* b, float* grad, long long n, float s0,
                    const float* s1_dev, const float* s2_dev, int relu, int accumulate,
                    void* stream);
-/* stx_style_loss(z, ...) and stx_mse(z, content, b*c*hw, 0, 2, mse_out, ...) (the content,
- * feature and feature-mse values of ContentLoss / FeatureReconstructionLoss at the
- * content tap, stransfer/network.py:155-164, 186-201) in one pass over z where the
- * Gram kernel allows it (c = 128 on the split path), else as the two calls.
- * ws >= stx_style_content_ws(b, c, hw); the deferred style-loss partials sit where
- * stx_style_loss_parts says, as for stx_style_loss. */
-size_t stx_style_content_ws(int b, int c, int hw);
-int stx_style_content_loss(const float* z, const float* target, float* coef, float* loss,
-                           int b, int c, int hw, int target_batched, float weight,
-                           float diag_alpha, const float* z_amax, const float* content,
-                           float* mse_out, void* ws, size_t ws_bytes, void* stream);
-/* stx_style_loss from precomputed Gram partials (stx_conv_params.gram_part; c <= 64 or
- * c == 128): parts [b][U][nparts][64][64] (U = 1, or 3 tiles for c = 128) summed in a
- * fixed order, then the same G, coef, loss and deferred loss partials
- * (ws >= stx_gram_ws(b, c, hw); stx_style_loss_parts). */
-int stx_style_loss_from_parts(const float* parts, int nparts, const float* target,
-                              float* g_out, float* coef, float* loss, int b, int c, int hw,
-                              int target_batched, float weight, float diag_alpha, void* ws,
-                              size_t ws_bytes, void* stream);
-/* stx_style_loss_from_parts plus the content tap's content / feature / feature-mse values
- * (stx_style_content_loss's mse_out) from the conv epilogue's MSE sums
- * (stx_conv_params.mse_parts: b * nparts pairs), finalized by the same launch. */
-int stx_style_content_loss_from_parts(const float* parts, int nparts, const float* target,
-                                      float* coef, float* loss, int b, int c, int hw,
-                                      int target_batched, float weight, float diag_alpha,
-                                      const float* mse_parts, float* mse_out, void* ws,
-                                      size_t ws_bytes, void* stream);
-/* Deferred Gram finalizes.  The *_deferred forms of stx_style_loss,
- * stx_style_content_loss and stx_style_loss_from_parts launch only their partial
- * kernel(s) (if any) and describe the finalize (G, coef, loss partials, the fused content
- * MSE) in *job; stx_gram_finalize_batch then runs up to STX_FIN_MAX such finalizes -- the
- * five StyleLoss taps of a forward -- in ONE launch, block for block the same arithmetic
- * (bit-identical to the immediate forms).  The loss partials land where
- * stx_style_loss_parts says; reduce them with stx_loss_finalize. */
+/* Deferred Gram finalizes: what one finalize launch does (G, coef, loss partials, the
+ * content MSE sums), as stx_style_loss fills it with a non-NULL `defer`.
+ * stx_gram_finalize_batch then runs up to STX_FIN_MAX such finalizes -- the five StyleLoss
+ * taps of a forward -- in ONE launch, block for block the same arithmetic (bit-identical to
+ * the immediate finalize).  The loss partials land where stx_style_loss_parts says; reduce
+ * them with stx_loss_finalize. */
 #define STX_FIN_MAX 8
 typedef struct stx_gram_fin_job {
   const float* parts;      /* partial slabs [b][ntiles][nsplit][64][64] */
@@ -490,25 +459,42 @@ typedef struct stx_gram_fin_job {
   int c, nsplit, b, cpad, mse_nparts;
   float* coef_amax;        /* optional amax group (zeroed): >= max|coef| over the batch */
 } stx_gram_fin_job;
-int stx_style_loss_deferred(const float* z, const float* target, float* coef, int b, int c,
-                            int hw, int target_batched, float weight, float diag_alpha,
-                            const float* z_amax, void* ws, size_t ws_bytes, stx_gram_fin_job* job,
-                            void* stream);
-int stx_style_content_loss_deferred(const float* z, const float* target, float* coef, int b,
-                                    int c, int hw, int target_batched, float weight,
-                                    float diag_alpha, const float* z_amax, const float* content,
-                                    float* mse_out, void* ws, size_t ws_bytes,
-                                    stx_gram_fin_job* job, void* stream);
-int stx_style_loss_from_parts_deferred(const float* parts, int nparts, const float* target,
-                                       float* coef, int b, int c, int hw, int target_batched,
-                                       float weight, float diag_alpha, void* ws, size_t ws_bytes,
-                                       stx_gram_fin_job* job, void* stream);
-int stx_style_content_loss_from_parts_deferred(const float* parts, int nparts,
-                                               const float* target, float* coef, int b, int c,
-                                               int hw, int target_batched, float weight,
-                                               float diag_alpha, const float* mse_parts,
-                                               float* mse_out, void* ws, size_t ws_bytes,
-                                               stx_gram_fin_job* job, void* stream);
+/* The style loss of one VGG tap, from exactly one of two sources:
+ *   z      features [b][c][hw]; the Gram partials are formed here (z_amax as for stx_gram)
+ *   parts  [b][U][nparts][64][64] partials a conv epilogue wrote (stx_conv_params.gram_part;
+ *          c <= 64: U = 1, c == 128: U = 3 tiles), summed in a fixed order
+ * and then G, the loss and the backward operator as above.  With the content companion
+ * (the content tap, stransfer/network.py:155-164, 186-201) mse_out[3] receives what
+ * stx_mse(z, content, b*c*hw, 0, 2, mse_out, ...) writes: from `content` [b][c][hw] with
+ * z (in the Gram's pass over z where its kernel allows, c = 128 on the split path, else a
+ * separate pass), or from `mse_parts` with parts (stx_conv_params.mse_parts: b * nparts
+ * pairs), finalized by the same launch.  content / mse_parts present iff mse_out is.
+ * ws >= stx_gram_ws(b, c, hw), or stx_style_content_ws(b, c, hw) with `content`.
+ * loss == NULL leaves the loss partials in ws (stx_style_loss_parts).  defer == NULL: the
+ * finalize runs in this call; else only the partial kernel(s) (if any) run, *defer
+ * describes the finalize for stx_gram_finalize_batch, and loss must be NULL.  Malformed
+ * structs are refused before any launch. */
+size_t stx_style_content_ws(int b, int c, int hw);
+typedef struct stx_style_loss_params {
+  const float* z;          /* source: features ... */
+  const float* parts;      /* ... or precomputed partials, */
+  int nparts;              /*     this many per tile */
+  const float* z_amax;     /* optional, with z */
+  const float* target;     /* [c][c], or [b][c][c] with target_batched */
+  int target_batched;
+  float* g_out;            /* optional G [b][c][c] */
+  float* coef;             /* optional A [b][cpad][cpad] */
+  float* loss;             /* optional device scalar */
+  int b, c, hw;
+  float weight, diag_alpha;
+  const float* content;    /* content companion with z ... */
+  const float* mse_parts;  /* ... or with parts */
+  float* mse_out;
+  void* ws;
+  size_t ws_bytes;
+  stx_gram_fin_job* defer;
+} stx_style_loss_params;
+int stx_style_loss(const stx_style_loss_params* p, void* stream);
 int stx_gram_finalize_batch(const stx_gram_fin_job* jobs, int njobs, void* stream);
 
 /* *out = sum_i w_host[i] * s[i]   (k <= 16 device scalars, fixed order) */
@@ -662,8 +648,6 @@ int stx_cin_mix(const stx_cin_job* jobs, int njobs, const float* mix, int n, int
                 void* stream);
 int stx_cin_param_grads(const stx_cin_job* jobs, int njobs, const float* mix, int n, int S,
                         void* stream);
-/* sizeof and last-member offset of stx_cin_job, as stx_abi_layout gives the older structs' */
-int stx_cin_abi_layout(long long* out, int n);
 
 /* nearest x2 upsample: y [nc][2h][2w];  backward dx[y][x] = sum of dy's 2x2 block */
 int stx_upsample2x_fwd(const float* x, float* y, int nc, int h, int w, void* stream);

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("STX_LIB", os.path.join(_HERE, "libstx.so"))
 STX_IN_RAW, STX_IN_RELU, STX_IN_RELU_POOL2, STX_IN_UPSAMPLE2, STX_IN_DILATE2 = range(5)
 STX_AMAX_SLOTS = 32  # an "amax" is a group of 32 floats whose max is the value (stx.h)
 STX_GRAM_GROUP = 8  # fused Gram partials per in-kernel group sum (stx_conv_params.gram_cnt)
-STX_ABI_VERSION = 9 # include/stx.h: the library must report the same revision
+STX_ABI_VERSION = 10 # include/stx.h: the library must report the same revision
 
 
 def knob(name: str, default: str) -> str:
@@ -101,6 +101,15 @@ class GramFinJob(C.Structure):
                 ("b", i32), ("cpad", i32), ("mse_nparts", i32), ("coef_amax", vp)]
 
 
+class StyleLossParams(C.Structure):
+    """Mirror of `stx_style_loss_params` (include/stx.h)."""
+    _fields_ = [("z", vp), ("parts", vp), ("nparts", i32), ("z_amax", vp), ("target", vp),
+                ("target_batched", i32), ("g_out", vp), ("coef", vp), ("loss", vp), ("b", i32),
+                ("c", i32), ("hw", i32), ("weight", f32), ("diag_alpha", f32), ("content", vp),
+                ("mse_parts", vp), ("mse_out", vp), ("ws", vp), ("ws_bytes", sz),
+                ("defer", C.POINTER(GramFinJob))]
+
+
 STX_FIN_MAX = 8
 STX_GUIDE_MAX = 4  # regions of a guided Gram (include/stx.h)
 
@@ -150,24 +159,8 @@ SIGNATURES = {
     "stx_gram_ws": (sz, [i32, i32, i32]),
     "stx_gram": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, sz, vp]),
     "stx_gram_coef_pitch": (i32, [i32]),
-    "stx_style_loss": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, sz,
-                             vp]),
-    "stx_style_loss_from_parts": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32,
-                                        vp, sz, vp]),
-    "stx_style_content_loss_from_parts": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, f32,
-                                                f32, vp, vp, vp, sz, vp]),
+    "stx_style_loss": (i32, [C.POINTER(StyleLossParams), vp]),
     "stx_style_content_ws": (sz, [i32, i32, i32]),
-    "stx_style_content_loss": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp,
-                                     vp, sz, vp]),
-    "stx_style_loss_deferred": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, sz,
-                                      C.POINTER(GramFinJob), vp]),
-    "stx_style_content_loss_deferred": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp,
-                                              vp, vp, sz, C.POINTER(GramFinJob), vp]),
-    "stx_style_loss_from_parts_deferred": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, f32, f32,
-                                                 vp, sz, C.POINTER(GramFinJob), vp]),
-    "stx_style_content_loss_from_parts_deferred": (i32, [vp, i32, vp, vp, i32, i32, i32, i32,
-                                                         f32, f32, vp, vp, vp, sz,
-                                                         C.POINTER(GramFinJob), vp]),
     "stx_gram_finalize_batch": (i32, [C.POINTER(GramFinJob), i32, vp]),
     "stx_gram_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, f32, i32, vp]),
     "stx_guided_style_ws": (sz, [i32, i32, i32, i32]),
@@ -200,7 +193,6 @@ SIGNATURES = {
                                i32, i32, vp, vp, sz, vp]),
     "stx_cin_mix": (i32, [C.POINTER(CinJob), i32, vp, i32, i32, vp]),
     "stx_cin_param_grads": (i32, [C.POINTER(CinJob), i32, vp, i32, i32, vp]),
-    "stx_cin_abi_layout": (i32, [vp, i32]),
     "stx_upsample2x_fwd": (i32, [vp, vp, i32, i32, i32, vp]),
     "stx_upsample2x_bwd": (i32, [vp, vp, i32, i32, i32, vp]),
     "stx_tv_ws": (sz, [i32, i32, i32, i32]),

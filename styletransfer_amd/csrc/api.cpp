@@ -42,16 +42,10 @@ extern "C" int stx_abi_layout(long long* out, int n) {
       (long long)sizeof(stx_loss_parts),   (long long)offsetof(stx_loss_parts, k),
       (long long)sizeof(stx_gram_fin_job), (long long)offsetof(stx_gram_fin_job, coef_amax),
       (long long)sizeof(stx_in_pgrad_job), (long long)offsetof(stx_in_pgrad_job, pad_),
-      (long long)sizeof(stx_image_meta),   (long long)offsetof(stx_image_meta, tmp_offset)};
-  const int m = (int)(sizeof(v) / sizeof(v[0]));
-  for (int i = 0; out && i < n && i < m; ++i) out[i] = v[i];
-  return m;
-}
-
-// the same for stx_cin_job, which came after that table's count was pinned
-extern "C" int stx_cin_abi_layout(long long* out, int n) {
-  const long long v[] = {(long long)sizeof(stx_cin_job),
-                         (long long)offsetof(stx_cin_job, accumulate)};
+      (long long)sizeof(stx_image_meta),   (long long)offsetof(stx_image_meta, tmp_offset),
+      (long long)sizeof(stx_cin_job),      (long long)offsetof(stx_cin_job, accumulate),
+      (long long)sizeof(stx_style_loss_params),
+      (long long)offsetof(stx_style_loss_params, defer)};
   const int m = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; out && i < n && i < m; ++i) out[i] = v[i];
   return m;

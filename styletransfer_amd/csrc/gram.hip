@@ -837,54 +837,43 @@ __device__ __forceinline__ void gram_finalize_body_g(
   }
 }
 
-__device__ __forceinline__ void gram_finalize_body(
-    const float* __restrict__ ws, int c, int nsplit, float scale, float* __restrict__ g_out,
-    const float* __restrict__ target, long long t_bstride, float* __restrict__ coef, int cpad,
-    float cA, float alpha, float* __restrict__ loss_parts, const float* __restrict__ mse_parts,
-    int mse_nparts, double mse_n, float* __restrict__ mse_out, int bx, int by,
-    float* __restrict__ coef_amax = nullptr) {
+// one block of the finalize `q` describes (stx_gram_fin_job: the one description of a
+// finalize, immediate or batched)
+__device__ __forceinline__ void gram_finalize_body(const stx_gram_fin_job& q, int bx, int by) {
   __shared__ float part[FKL * (FEL + 1)];
   __shared__ float red[FNT / 64];
   // block (0, 0) also finalizes the content / feature MSE partials of a fused content
   // pass (gram_tri_f16_kernel<true>): the launch a separate mse2 finalize would take
-  if (mse_out && bx == 0 && by == 0) {
+  if (q.mse_out && bx == 0 && by == 0) {
     float s = 0.f, sr = 0.f;
-    for (int i = threadIdx.x; i < mse_nparts; i += FNT) {
-      s += mse_parts[2 * i];
-      sr += mse_parts[2 * i + 1];
+    for (int i = threadIdx.x; i < q.mse_nparts; i += FNT) {
+      s += q.mse_parts[2 * i];
+      sr += q.mse_parts[2 * i + 1];
     }
     s = block_sum<FNT>(s, red);
     sr = block_sum<FNT>(sr, red);
     if (threadIdx.x == 0) {
-      const float mr = (float)(sr / mse_n);
-      mse_out[0] = (float)(s / mse_n);
-      mse_out[1] = (float)((double)(mr * mr) / mse_n);
-      mse_out[2] = mr;
+      const float mr = (float)(sr / q.mse_n);
+      q.mse_out[0] = (float)(s / q.mse_n);
+      q.mse_out[1] = (float)((double)(mr * mr) / q.mse_n);
+      q.mse_out[2] = mr;
     }
   }
-  switch (fin_groups(nsplit)) {
-    case 4:
-      gram_finalize_body_g<4>(ws, c, nsplit, scale, g_out, target, t_bstride, coef, cpad, cA,
-                              alpha, loss_parts, bx, by, part, coef_amax);
-      break;
-    case 2:
-      gram_finalize_body_g<2>(ws, c, nsplit, scale, g_out, target, t_bstride, coef, cpad, cA,
-                              alpha, loss_parts, bx, by, part, coef_amax);
-      break;
-    default:
-      gram_finalize_body_g<1>(ws, c, nsplit, scale, g_out, target, t_bstride, coef, cpad, cA,
-                              alpha, loss_parts, bx, by, part, coef_amax);
+#define STX_FIN_BODY(G)                                                                      \
+  gram_finalize_body_g<G>(q.parts, q.c, q.nsplit, q.scale, q.g_out, q.target, q.t_bstride,   \
+                          q.coef, q.cpad, q.cA, q.alpha, q.loss_parts, bx, by, part,         \
+                          q.coef_amax)
+  switch (fin_groups(q.nsplit)) {
+    case 4: STX_FIN_BODY(4); break;
+    case 2: STX_FIN_BODY(2); break;
+    default: STX_FIN_BODY(1);
   }
+#undef STX_FIN_BODY
 }
 
-__global__ void __launch_bounds__(FNT)
-gram_finalize_kernel(const float* __restrict__ ws, int c, int nsplit, float scale,
-                     float* __restrict__ g_out, const float* __restrict__ target, long long t_bstride,
-                     float* __restrict__ coef, int cpad, float cA, float alpha,
-                     float* __restrict__ loss_parts, const float* __restrict__ mse_parts = nullptr,
-                     int mse_nparts = 0, double mse_n = 1.0, float* __restrict__ mse_out = nullptr) {
-  gram_finalize_body(ws, c, nsplit, scale, g_out, target, t_bstride, coef, cpad, cA, alpha,
-                     loss_parts, mse_parts, mse_nparts, mse_n, mse_out, blockIdx.x, blockIdx.y);
+// grid (ntu * fin_blocks_per_tile(nsplit), b)
+__global__ void __launch_bounds__(FNT) gram_finalize_kernel(stx_gram_fin_job q) {
+  gram_finalize_body(q, blockIdx.x, blockIdx.y);
 }
 
 // the finalizes of several style losses (one per VGG tap) in ONE launch: block ranges
@@ -901,9 +890,7 @@ __global__ void __launch_bounds__(FNT) gram_finalize_batch_kernel(FinBatch fb) {
   const stx_gram_fin_job& q = fb.job[j];
   const int local = blockIdx.x - fb.blk0[j];
   const int nt = cdiv(q.c, GT), nbx = nt * (nt + 1) / 2 * fin_blocks_per_tile(q.nsplit);
-  gram_finalize_body(q.parts, q.c, q.nsplit, q.scale, q.g_out, q.target, q.t_bstride, q.coef,
-                     q.cpad, q.cA, q.alpha, q.loss_parts, q.mse_parts, q.mse_nparts, q.mse_n,
-                     q.mse_out, local % nbx, local / nbx, q.coef_amax);
+  gram_finalize_body(q, local % nbx, local / nbx);
 }
 
 // one wave: the fixed-order sum of n loss partials (4 lane-strided accumulators, then a
@@ -995,7 +982,7 @@ static size_t gram_ws_bytes(int b, int c, int hw) {
   return off + ((size_t)nparts + 64) * sizeof(float);
 }
 
-// content / feature MSE companion of a style loss (stx_style_content_loss)
+// content / feature MSE companion of a style loss (stx_style_loss_params.content)
 struct MseCompanion {
   const float* content;  // [b][c][hw], the content target
   float* out;            // [3]: content mse, feature loss, feature mse (stx_mse mode 2)
@@ -1003,54 +990,20 @@ struct MseCompanion {
   size_t parts_bytes;
 };
 
-static void fill_job(stx_gram_fin_job* job, const float* parts, int c, int nsplit, float scale,
-                     float* g_out, const float* target, long long t_bstride, float* coef,
-                     int cpad, float cA, float alpha, float* loss_parts, const float* mse_parts,
-                     int mse_nparts, double mse_n, float* mse_out, int b) {
-  *job = stx_gram_fin_job{};
-  job->parts = parts;
-  job->c = c;
-  job->nsplit = nsplit;
-  job->b = b;
-  job->scale = scale;
-  job->g_out = g_out;
-  job->target = target;
-  job->t_bstride = t_bstride;
-  job->coef = coef;
-  job->cpad = cpad;
-  job->cA = cA;
-  job->alpha = alpha;
-  job->loss_parts = loss_parts;
-  job->mse_parts = mse_parts;
-  job->mse_nparts = mse_nparts;
-  job->mse_n = mse_n;
-  job->mse_out = mse_out;
-}
-
-static int gram_run(const float* z, int b, int c, int hw, float scale, float* g_out,
-                    const float* target, long long t_bstride, float* coef, float cA, float alpha, float* loss,
-                    float loss_inv, const float* z_amax, void* ws, size_t ws_bytes,
-                    hipStream_t st, const MseCompanion* mse = nullptr,
-                    stx_gram_fin_job* defer = nullptr) {
-  if (b <= 0 || c <= 0 || hw <= 0 || !z) {
-    set_error("gram: invalid dims");
-    return STX_E_INVALID;
-  }
+// Gram partials of z [q.b][q.c][hw] into ws (>= gram_ws_bytes); fills in q's parts, nsplit
+// and loss_parts.  With `mse`, and where the kernel that runs can take the content pass
+// along (the tri kernel), also q's MSE fields: returns whether it did.
+static bool gram_partials(const float* z, int hw, const float* z_amax, void* ws, hipStream_t st,
+                          stx_gram_fin_job& q, const MseCompanion* mse = nullptr) {
+  const int b = q.b, c = q.c;
   const bool f16 = z_amax && hw % 8 == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0;
   int nsplit, split_len, ntu;
   if (f16)
     gram_geometry16(c, hw, b, nsplit, split_len, ntu);
   else
     gram_geometry(c, hw, b, nsplit, split_len, ntu);
-  const size_t need = gram_ws_bytes(b, c, hw);
-  if (!ws || ws_bytes < need) {
-    set_error("gram: workspace %zu < %zu", ws_bytes, need);
-    return STX_E_WORKSPACE;
-  }
   float* slabs = (float*)ws;
-  float* parts = (float*)((char*)ws + gram_parts_offset(b, c, hw, nullptr));
-  const MseCompanion* mse_fin = nullptr;
-  int mse_nparts = 0;
+  bool fused = false;
   if (f16 && gram_tri_on(c, hw)) {
     nsplit = gram_tri_splits(c, hw, b);
     split_len = rup(cdiv(hw, nsplit), 64);
@@ -1059,9 +1012,10 @@ static int gram_run(const float* z, int b, int c, int hw, float scale, float* g_
         mse->parts_bytes >= (size_t)2 * b * nsplit * sizeof(float)) {
       hipLaunchKernelGGL(gram_tri_f16_kernel<true>, dim3(nsplit, 1, b), dim3(256), 0, st,
                          z, slabs, hw, nsplit, split_len, z_amax, mse->content, mse->parts);
-      mse_fin = mse;  // finalized by the Gram finalize below
-      mse_nparts = b * nsplit;
-      mse = nullptr;  // done
+      fused = true;  // finalized by the Gram finalize
+      q.mse_parts = mse->parts;
+      q.mse_nparts = b * nsplit;
+      q.mse_out = mse->out;
     } else
       hipLaunchKernelGGL(gram_tri_f16_kernel<false>, dim3(nsplit, 1, b), dim3(256), 0, st, z, slabs,
                          hw, nsplit, split_len, z_amax);
@@ -1084,26 +1038,26 @@ static int gram_run(const float* z, int b, int c, int hw, float scale, float* g_
   } else
     hipLaunchKernelGGL(gram_partial_kernel, dim3(nsplit, ntu, b), dim3(256), 0, st, z, slabs, c,
                        hw, nsplit, split_len);
-  const int cpad = stx_gram_coef_pitch(c);
-  if (defer) {  // the finalize joins a stx_gram_finalize_batch launch
-    fill_job(defer, slabs, c, nsplit, scale, g_out, target, t_bstride, coef, cpad, cA, alpha,
-             parts, mse_fin ? mse_fin->parts : nullptr, mse_nparts, (double)b * c * hw,
-             mse_fin ? mse_fin->out : nullptr, b);
-  } else {
-    hipLaunchKernelGGL(gram_finalize_kernel, dim3(ntu * fin_blocks_per_tile(nsplit), b), dim3(FNT), 0, st, slabs, c,
-                       nsplit, scale, g_out, target, t_bstride, coef, cpad, cA, alpha, parts,
-                       mse_fin ? mse_fin->parts : nullptr, mse_nparts, (double)b * c * hw,
-                       mse_fin ? mse_fin->out : nullptr);
+  q.parts = slabs;
+  q.nsplit = nsplit;
+  q.loss_parts = (float*)((char*)ws + gram_parts_offset(b, c, hw, nullptr));
+  return fused;
+}
+
+// The one finalize path: copied out for a later stx_gram_finalize_batch, or launched now,
+// followed by the reduction of its loss partials into *loss (if asked for).
+static void gram_finalize(const stx_gram_fin_job& q, stx_gram_fin_job* defer, float* loss,
+                          hipStream_t st) {
+  if (defer) {
+    *defer = q;
+    return;
   }
-  if (target && loss && !defer)
-    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(64), 0, st, parts, b * ntu * FSUB,
-                       loss_inv, loss);
-  if (mse) {  // not fused (another Gram kernel ran): the separate content pass
-    const int rc = stx_mse(z, mse->content, (long long)b * c * hw, 0, 2, mse->out, nullptr, 1.f,
-                           mse->parts, mse->parts_bytes, st);
-    if (rc) return rc;
-  }
-  return check_launch("gram");
+  const int nt = cdiv(q.c, GT), ntu = nt * (nt + 1) / 2;
+  hipLaunchKernelGGL(gram_finalize_kernel, dim3(ntu * fin_blocks_per_tile(q.nsplit), q.b),
+                     dim3(FNT), 0, st, q);
+  if (q.target && loss)
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(64), 0, st, q.loss_parts,
+                       q.b * ntu * FSUB, (float)(1.0 / ((double)q.b * q.c * q.c)), loss);
 }
 
 }  // namespace stx
@@ -1162,52 +1116,24 @@ extern "C" int stx_gram_coef_pitch(int c) { return c <= 64 ? rup(c, 64) : rup(c,
 
 extern "C" int stx_gram(const float* z, float* g, int b, int c, int hw, float scale,
                         const float* z_amax, void* ws, size_t ws_bytes, void* stream) {
-  return gram_run(z, b, c, hw, scale, g, nullptr, 0, nullptr, 0.f, 0.f, nullptr, 0.f, z_amax, ws,
-                  ws_bytes,
-                  (hipStream_t)stream);
-}
-
-static int style_loss_impl(const float* z, const float* target, float* g_out, float* coef,
-                           float* loss, int b, int c, int hw, int target_batched, float weight,
-                           float diag_alpha, const float* z_amax, void* ws, size_t ws_bytes,
-                           void* stream, stx_gram_fin_job* defer) {
-  if (!target) {  // loss == NULL: partials stay in ws (stx_style_loss_parts)
-    set_error("stx_style_loss: target is required");
+  if (b <= 0 || c <= 0 || hw <= 0 || !z) {
+    set_error("gram: invalid dims");
     return STX_E_INVALID;
   }
-  hipStream_t st = (hipStream_t)stream;
-  const double n = (double)c * hw;
-  const float scale = (float)(1.0 / n);
-  // d(weight*mean((G-T)^2))/dF_b = weight * 2(G-T)/(B C^2) * 2 F_b / N   (G symmetric)
-  const float cA = (float)(weight * 4.0 / ((double)b * c * c * n));
-  if (coef && stx_gram_coef_pitch(c) != c) {  // zero the padding (finalize writes c x c)
-    const int cpad = stx_gram_coef_pitch(c);
-    const long long cnt = (long long)b * cpad * cpad;
-    hipLaunchKernelGGL(zero_kernel, dim3((int)std::min<long long>((cnt + 255) / 256, 2048)),
-                       dim3(256), 0, st, coef, cnt);
+  const size_t need = gram_ws_bytes(b, c, hw);
+  if (!ws || ws_bytes < need) {
+    set_error("gram: workspace %zu < %zu", ws_bytes, need);
+    return STX_E_WORKSPACE;
   }
-  return gram_run(z, b, c, hw, scale, g_out, target, target_batched ? (long long)c * c : 0, coef, cA, diag_alpha, loss,
-                  (float)(1.0 / ((double)b * c * c)), z_amax, ws, ws_bytes, st, nullptr, defer);
-}
-
-extern "C" int stx_style_loss(const float* z, const float* target, float* g_out, float* coef,
-                              float* loss, int b, int c, int hw, int target_batched, float weight,
-                              float diag_alpha, const float* z_amax, void* ws, size_t ws_bytes,
-                              void* stream) {
-  return style_loss_impl(z, target, g_out, coef, loss, b, c, hw, target_batched, weight,
-                         diag_alpha, z_amax, ws, ws_bytes, stream, nullptr);
-}
-
-extern "C" int stx_style_loss_deferred(const float* z, const float* target, float* coef, int b,
-                                       int c, int hw, int target_batched, float weight,
-                                       float diag_alpha, const float* z_amax, void* ws,
-                                       size_t ws_bytes, stx_gram_fin_job* job, void* stream) {
-  if (!job) {
-    set_error("stx_style_loss_deferred: job is required");
-    return STX_E_INVALID;
-  }
-  return style_loss_impl(z, target, nullptr, coef, nullptr, b, c, hw, target_batched, weight,
-                         diag_alpha, z_amax, ws, ws_bytes, stream, job);
+  stx_gram_fin_job q{};
+  q.b = b;
+  q.c = c;
+  q.scale = scale;
+  q.g_out = g;
+  q.cpad = stx_gram_coef_pitch(c);
+  gram_partials(z, hw, z_amax, ws, (hipStream_t)stream, q);
+  gram_finalize(q, nullptr, nullptr, (hipStream_t)stream);
+  return check_launch("gram");
 }
 
 static size_t style_content_parts_bytes(int b, int c, int hw) {
@@ -1219,159 +1145,83 @@ extern "C" size_t stx_style_content_ws(int b, int c, int hw) {
   return rup((long long)gram_ws_bytes(b, c, hw), 256) + style_content_parts_bytes(b, c, hw);
 }
 
-static int style_content_impl(const float* z, const float* target, float* coef, float* loss,
-                              int b, int c, int hw, int target_batched, float weight,
-                              float diag_alpha, const float* z_amax, const float* content,
-                              float* mse_out, void* ws, size_t ws_bytes, void* stream,
-                              stx_gram_fin_job* defer) {
-  if (!target || !content || !mse_out) {
-    set_error("stx_style_content_loss: target, content and mse_out are required");
+// refused before any launch (STX_E_INVALID with the reason, STX_E_WORKSPACE)
+static int style_loss_check(const stx_style_loss_params* p) {
+  const char* why = nullptr;
+  if (!p || !p->target)  // loss == NULL: partials stay in ws (stx_style_loss_parts)
+    why = "target is required";
+  else if ((p->z != nullptr) == (p->parts != nullptr))
+    why = "exactly one of z and parts is required";
+  else if (p->b <= 0 || p->c <= 0 || p->hw <= 0)
+    why = "invalid dims";
+  else if (p->parts && (p->nparts <= 0 || (p->c > GT && p->c != 2 * GT)))
+    why = "parts need nparts > 0 and c <= 64 or c == 128";
+  else if (p->z ? p->mse_parts != nullptr : p->content != nullptr)
+    why = "content goes with z, mse_parts with parts";
+  else if ((p->content || p->mse_parts) != (p->mse_out != nullptr))
+    why = "content / mse_parts and mse_out go together";
+  else if (p->defer && p->loss)
+    why = "a deferred finalize has no loss (stx_loss_finalize)";
+  if (why) {
+    set_error("stx_style_loss: %s", why);
     return STX_E_INVALID;
   }
-  if (!ws || ws_bytes < stx_style_content_ws(b, c, hw)) {
-    set_error("stx_style_content_loss: workspace too small");
+  const size_t need = p->content ? stx_style_content_ws(p->b, p->c, p->hw)
+                                 : gram_ws_bytes(p->b, p->c, p->hw);
+  if (!p->ws || p->ws_bytes < need) {
+    set_error("stx_style_loss: workspace %zu < %zu", p->ws_bytes, need);
     return STX_E_WORKSPACE;
   }
+  return STX_OK;
+}
+
+extern "C" int stx_style_loss(const stx_style_loss_params* p, void* stream) {
+  if (const int rc = style_loss_check(p)) return rc;
   hipStream_t st = (hipStream_t)stream;
+  const int b = p->b, c = p->c, hw = p->hw;
   const double n = (double)c * hw;
-  const float scale = (float)(1.0 / n);
-  const float cA = (float)(weight * 4.0 / ((double)b * c * c * n));
-  const int cpad = stx_gram_coef_pitch(c);
-  if (coef && cpad != c) {
-    const long long cnt = (long long)b * cpad * cpad;
+  stx_gram_fin_job q{};
+  q.b = b;
+  q.c = c;
+  q.cpad = stx_gram_coef_pitch(c);
+  q.scale = (float)(1.0 / n);
+  // d(weight*mean((G-T)^2))/dF_b = weight * 2(G-T)/(B C^2) * 2 F_b / N   (G symmetric)
+  q.cA = (float)(p->weight * 4.0 / ((double)b * c * c * n));
+  q.alpha = p->diag_alpha;
+  q.g_out = p->g_out;
+  q.target = p->target;
+  q.t_bstride = p->target_batched ? (long long)c * c : 0;
+  q.coef = p->coef;
+  q.mse_n = (double)b * c * hw;
+  if (p->coef && q.cpad != c) {  // zero the padding (finalize writes c x c)
+    const long long cnt = (long long)b * q.cpad * q.cpad;
     hipLaunchKernelGGL(zero_kernel, dim3((int)std::min<long long>((cnt + 255) / 256, 2048)),
-                       dim3(256), 0, st, coef, cnt);
+                       dim3(256), 0, st, p->coef, cnt);
   }
-  const size_t gb = rup((long long)gram_ws_bytes(b, c, hw), 256);
-  MseCompanion m{content, mse_out, (float*)((char*)ws + gb), ws_bytes - gb};
-  return gram_run(z, b, c, hw, scale, nullptr, target, target_batched ? (long long)c * c : 0,
-                  coef, cA, diag_alpha, loss, (float)(1.0 / ((double)b * c * c)), z_amax, ws, gb,
-                  st, &m, defer);
-}
-
-extern "C" int stx_style_content_loss(const float* z, const float* target, float* coef,
-                                      float* loss, int b, int c, int hw, int target_batched,
-                                      float weight, float diag_alpha, const float* z_amax,
-                                      const float* content, float* mse_out, void* ws,
-                                      size_t ws_bytes, void* stream) {
-  return style_content_impl(z, target, coef, loss, b, c, hw, target_batched, weight, diag_alpha,
-                            z_amax, content, mse_out, ws, ws_bytes, stream, nullptr);
-}
-
-extern "C" int stx_style_content_loss_deferred(const float* z, const float* target, float* coef,
-                                               int b, int c, int hw, int target_batched,
-                                               float weight, float diag_alpha,
-                                               const float* z_amax, const float* content,
-                                               float* mse_out, void* ws, size_t ws_bytes,
-                                               stx_gram_fin_job* job, void* stream) {
-  if (!job) {
-    set_error("stx_style_content_loss_deferred: job is required");
-    return STX_E_INVALID;
+  MseCompanion m{};
+  if (p->content) {  // the content pass's partials follow the Gram's workspace
+    const size_t gb = rup((long long)gram_ws_bytes(b, c, hw), 256);
+    m = {p->content, p->mse_out, (float*)((char*)p->ws + gb), p->ws_bytes - gb};
   }
-  return style_content_impl(z, target, coef, nullptr, b, c, hw, target_batched, weight,
-                            diag_alpha, z_amax, content, mse_out, ws, ws_bytes, stream, job);
-}
-
-// gparts: [b][ntu][nparts][64 x 64] (ntu = 1 for c <= 64, 3 for c = 128: the fused conv
-// epilogue tiles, stx_conv_params.gram_part); mse_parts (c = 128, the content tap): the
-// epilogue's 2 sums per block, b * nparts pairs, finalized into mse_out like
-// gram_tri_f16_kernel<true>'s
-static int from_parts_impl(const float* gparts, int nparts, const float* target, float* g_out,
-                           float* coef, float* loss, int b, int c, int hw, int target_batched,
-                           float weight, float diag_alpha, void* ws, size_t ws_bytes,
-                           void* stream, stx_gram_fin_job* defer,
-                           const float* mse_parts = nullptr, float* mse_out = nullptr) {
-  if (!gparts || !target || nparts <= 0 || b <= 0 || c <= 0 || (c > GT && c != 2 * GT) ||
-      hw <= 0) {
-    set_error("stx_style_loss_from_parts: invalid arguments (c <= 64 or c == 128)");
-    return STX_E_INVALID;
+  bool mse_pass = false;  // the content sums as a pass of their own (stx_mse)
+  if (p->z) {
+    const bool fused = gram_partials(p->z, hw, p->z_amax, p->ws, st, q, p->content ? &m : nullptr);
+    mse_pass = p->content && !fused;
+  } else {  // [b][ntu][nparts][64 x 64] from the conv epilogue, its MSE sums b * nparts pairs
+    q.parts = p->parts;
+    q.nsplit = p->nparts;
+    q.loss_parts = (float*)((char*)p->ws + gram_parts_offset(b, c, hw, nullptr));
+    q.mse_parts = p->mse_parts;
+    q.mse_nparts = p->mse_parts ? b * p->nparts : 0;
+    q.mse_out = p->mse_parts ? p->mse_out : nullptr;
   }
-  if ((mse_parts != nullptr) != (mse_out != nullptr)) {
-    set_error("stx_style_content_loss_from_parts: mse_parts and mse_out go together");
-    return STX_E_INVALID;
+  gram_finalize(q, p->defer, p->loss, st);
+  if (mse_pass) {  // not fused (another Gram kernel ran)
+    const int rc = stx_mse(p->z, m.content, (long long)b * c * hw, 0, 2, m.out, nullptr, 1.f,
+                           m.parts, m.parts_bytes, st);
+    if (rc) return rc;
   }
-  const int nt = cdiv(c, GT), ntu = nt * (nt + 1) / 2;
-  const size_t need = gram_ws_bytes(b, c, hw);
-  if (!ws || ws_bytes < need) {
-    set_error("stx_style_loss_from_parts: workspace %zu < %zu", ws_bytes, need);
-    return STX_E_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const double n = (double)c * hw;
-  const float cA = (float)(weight * 4.0 / ((double)b * c * c * n));
-  const int cpad = stx_gram_coef_pitch(c);
-  if (coef && cpad != c) {
-    const long long cnt = (long long)b * cpad * cpad;
-    hipLaunchKernelGGL(zero_kernel, dim3((int)std::min<long long>((cnt + 255) / 256, 2048)),
-                       dim3(256), 0, st, coef, cnt);
-  }
-  float* lparts = (float*)((char*)ws + gram_parts_offset(b, c, hw, nullptr));
-  const int mse_nparts = mse_parts ? b * nparts : 0;
-  const double mse_n = (double)b * c * hw;
-  if (defer) {
-    fill_job(defer, gparts, c, nparts, (float)(1.0 / n), g_out, target,
-             target_batched ? (long long)c * c : 0ll, coef, cpad, cA, diag_alpha, lparts,
-             mse_parts, mse_nparts, mse_n, mse_out, b);
-    return check_launch("stx_style_loss_from_parts_deferred");
-  }
-  hipLaunchKernelGGL(gram_finalize_kernel, dim3(ntu * fin_blocks_per_tile(nparts), b), dim3(FNT),
-                     0, st, gparts, c, nparts, (float)(1.0 / n), g_out, target,
-                     target_batched ? (long long)c * c : 0ll, coef, cpad, cA, diag_alpha, lparts,
-                     mse_parts, mse_nparts, mse_n, mse_out);
-  if (loss)
-    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(64), 0, st, lparts, b * ntu * FSUB,
-                       (float)(1.0 / ((double)b * c * c)), loss);
-  return check_launch("stx_style_loss_from_parts");
-}
-
-extern "C" int stx_style_content_loss_from_parts(const float* gparts, int nparts,
-                                                 const float* target, float* coef, float* loss,
-                                                 int b, int c, int hw, int target_batched,
-                                                 float weight, float diag_alpha,
-                                                 const float* mse_parts, float* mse_out, void* ws,
-                                                 size_t ws_bytes, void* stream) {
-  if (!mse_parts || !mse_out) {
-    set_error("stx_style_content_loss_from_parts: mse_parts and mse_out are required");
-    return STX_E_INVALID;
-  }
-  return from_parts_impl(gparts, nparts, target, nullptr, coef, loss, b, c, hw, target_batched,
-                         weight, diag_alpha, ws, ws_bytes, stream, nullptr, mse_parts, mse_out);
-}
-
-extern "C" int stx_style_content_loss_from_parts_deferred(
-    const float* gparts, int nparts, const float* target, float* coef, int b, int c, int hw,
-    int target_batched, float weight, float diag_alpha, const float* mse_parts, float* mse_out,
-    void* ws, size_t ws_bytes, stx_gram_fin_job* job, void* stream) {
-  if (!job || !mse_parts || !mse_out) {
-    set_error("stx_style_content_loss_from_parts_deferred: job, mse_parts and mse_out are "
-              "required");
-    return STX_E_INVALID;
-  }
-  return from_parts_impl(gparts, nparts, target, nullptr, coef, nullptr, b, c, hw,
-                         target_batched, weight, diag_alpha, ws, ws_bytes, stream, job, mse_parts,
-                         mse_out);
-}
-
-extern "C" int stx_style_loss_from_parts(const float* gparts, int nparts, const float* target,
-                                         float* g_out, float* coef, float* loss, int b, int c,
-                                         int hw, int target_batched, float weight,
-                                         float diag_alpha, void* ws, size_t ws_bytes,
-                                         void* stream) {
-  return from_parts_impl(gparts, nparts, target, g_out, coef, loss, b, c, hw, target_batched,
-                         weight, diag_alpha, ws, ws_bytes, stream, nullptr);
-}
-
-extern "C" int stx_style_loss_from_parts_deferred(const float* gparts, int nparts,
-                                                  const float* target, float* coef, int b, int c,
-                                                  int hw, int target_batched, float weight,
-                                                  float diag_alpha, void* ws, size_t ws_bytes,
-                                                  stx_gram_fin_job* job, void* stream) {
-  if (!job) {
-    set_error("stx_style_loss_from_parts_deferred: job is required");
-    return STX_E_INVALID;
-  }
-  return from_parts_impl(gparts, nparts, target, nullptr, coef, nullptr, b, c, hw,
-                         target_batched, weight, diag_alpha, ws, ws_bytes, stream, job);
+  return check_launch("stx_style_loss");
 }
 
 extern "C" int stx_gram_finalize_batch(const stx_gram_fin_job* jobs, int njobs, void* stream) {

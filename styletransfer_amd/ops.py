@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import functools
 import gc
 
 import torch
@@ -773,46 +774,65 @@ class FinalizeBatch:
         self.jobs, self.keep = [], []
 
 
+@functools.lru_cache(maxsize=None)
+def _style_dims(b, c, hw, content):
+    """A tap's host-side constants: workspace bytes (stx_style_content_ws with the content
+    companion), byte offset and count of its loss partials in it, coef pitch."""
+    L = lib()
+    npart = C.c_int()
+    off = L.stx_style_loss_parts(b, c, hw, C.byref(npart))
+    need = (L.stx_style_content_ws if content else L.stx_gram_ws)(b, c, hw)
+    return need, off, npart.value, L.stx_gram_coef_pitch(c)
+
+
+def _style_loss(b, c, hw, target, device, weight, diag_alpha, coef, defer_ws, fin, *,
+                want_coef=True, loss=None, nparts=0, **source):
+    """The one stx_style_loss call behind style_loss, style_content_loss and
+    style_loss_from_parts.  source: the tensors (or None) of N.StyleLossParams by field
+    name -- z, z_amax, g_out, content, mse_out, or parts (with nparts), mse_parts, mse_out.
+    Returns (loss, coef), the loss as the deferred (ptr, nparts, inv) triple with defer_ws."""
+    _req(target, "target")
+    # target [c][c] / [1][c][c] broadcast over the batch (expand_as), or [b][c][c]
+    tb = target.numel() == b * c * c and b > 1
+    if not tb and target.numel() != c * c:
+        raise ValueError(f"style target {tuple(target.shape)} cannot expand to ({b},{c},{c})")
+    need, off, npart, cp = _style_dims(b, c, hw, source.get("content") is not None)
+    if not want_coef:
+        coef = None
+    elif coef is None:
+        coef = torch.empty((b, cp, cp), device=device, dtype=torch.float32)
+    if defer_ws is not None:
+        assert defer_ws.numel() >= need, (defer_ws.numel(), need)
+        wp, wn = defer_ws.data_ptr(), defer_ws.numel()
+    else:
+        wp, wn = WS.get(need, device)
+    source.update(target=target, coef=coef, loss=loss)
+    p = N.StyleLossParams(target_batched=int(tb), b=b, c=c, hw=hw, weight=float(weight),
+                          diag_alpha=float(diag_alpha), ws=wp, ws_bytes=wn, nparts=int(nparts),
+                          **{k: t.data_ptr() for k, t in source.items() if t is not None})
+    if fin is not None:  # finalize deferred to fin.flush()
+        assert defer_ws is not None
+        p.defer = C.pointer(fin.new())
+    check(lib().stx_style_loss(C.byref(p), _stream()), "stx_style_loss")
+    if defer_ws is None:
+        return loss, coef
+    return (wp + off, npart, 1.0 / (b * c * c)), coef
+
+
 def style_loss(z, target, weight=1.0, diag_alpha=0.0, want_coef=True, g_out=None, loss=None,
                coef=None, z_amax=None, defer_ws=None, fin=None):
     """mean((gram(z) - target)^2) -> 0-d loss; coef = d(weight*loss)/dz operator.
     defer_ws (uint8 device buffer >= stx_gram_ws): the loss is not reduced here; its
     partials stay in defer_ws for loss_finalize (returns (LossPart, coef))."""
     _req(z, "z")
-    _req(target, "target")
     b, c = z.shape[:2]
-    hw = z[0, 0].numel()
-    # target [c][c] / [1][c][c] broadcast over the batch (expand_as), or [b][c][c]
-    tb = target.numel() == b * c * c and b > 1
-    if not tb and target.numel() != c * c:
-        raise ValueError(f"style target {tuple(target.shape)} cannot expand to ({b},{c},{c})")
     if loss is None and defer_ws is None:
         loss = torch.empty((), device=z.device, dtype=torch.float32)
-    if want_coef and coef is None:
-        cp = coef_pitch(c)
-        coef = torch.empty((b, cp, cp), device=z.device, dtype=torch.float32)
-    L = lib()
-    need = L.stx_gram_ws(b, c, hw)
-    if defer_ws is not None:
-        assert defer_ws.numel() >= need, (defer_ws.numel(), need)
-        wp, wn = defer_ws.data_ptr(), defer_ws.numel()
-    else:
-        wp, wn = WS.get(need, z.device)
-    if fin is not None:  # finalize deferred to fin.flush()
-        assert defer_ws is not None and g_out is None and want_coef
-        check(L.stx_style_loss_deferred(z.data_ptr(), target.data_ptr(), coef.data_ptr(), b, c,
-                                        hw, int(tb), float(weight), float(diag_alpha),
-                                        _p(z_amax), wp, wn, C.byref(fin.new()), _stream()),
-              "stx_style_loss_deferred")
-    else:
-        check(L.stx_style_loss(z.data_ptr(), target.data_ptr(), _p(g_out), _p(coef) if want_coef
-                               else None, _p(loss), b, c, hw, int(tb), float(weight),
-                               float(diag_alpha), _p(z_amax), wp, wn, _stream()), "stx_style_loss")
-    if defer_ws is not None:
-        npart = C.c_int()
-        off = L.stx_style_loss_parts(b, c, hw, C.byref(npart))
-        return (wp + off, npart.value, 1.0 / (b * c * c)), (coef if want_coef else None)
-    return loss, (coef if want_coef else None)
+    if fin is not None:
+        assert g_out is None and want_coef
+    return _style_loss(b, c, z[0, 0].numel(), target, z.device, weight, diag_alpha, coef,
+                       defer_ws, fin, want_coef=want_coef, loss=loss, z=z, z_amax=z_amax,
+                       g_out=g_out)
 
 
 def style_content_loss(z, target, content, mse_out, weight=1.0, diag_alpha=0.0, coef=None,
@@ -821,35 +841,12 @@ def style_content_loss(z, target, content, mse_out, weight=1.0, diag_alpha=0.0, 
     one pass over z where the Gram kernel allows it.  defer_ws >= stx_style_content_ws.
     Returns (deferred LossPart, coef)."""
     _req(z, "z")
-    _req(target, "target")
     _req(content, "content")
     assert content.numel() == z.numel() and mse_out.numel() >= 3
+    assert defer_ws is not None
     b, c = z.shape[:2]
-    hw = z[0, 0].numel()
-    tb = target.numel() == b * c * c and b > 1
-    if not tb and target.numel() != c * c:
-        raise ValueError(f"style target {tuple(target.shape)} cannot expand to ({b},{c},{c})")
-    if coef is None:
-        cp = coef_pitch(c)
-        coef = torch.empty((b, cp, cp), device=z.device, dtype=torch.float32)
-    L = lib()
-    need = L.stx_style_content_ws(b, c, hw)
-    assert defer_ws is not None and defer_ws.numel() >= need, need
-    wp, wn = defer_ws.data_ptr(), defer_ws.numel()
-    if fin is not None:
-        check(L.stx_style_content_loss_deferred(z.data_ptr(), target.data_ptr(), coef.data_ptr(),
-                                                b, c, hw, int(tb), float(weight),
-                                                float(diag_alpha), _p(z_amax), content.data_ptr(),
-                                                mse_out.data_ptr(), wp, wn, C.byref(fin.new()),
-                                                _stream()), "stx_style_content_loss_deferred")
-    else:
-        check(L.stx_style_content_loss(z.data_ptr(), target.data_ptr(), coef.data_ptr(), None, b,
-                                       c, hw, int(tb), float(weight), float(diag_alpha),
-                                       _p(z_amax), content.data_ptr(), mse_out.data_ptr(), wp, wn,
-                                       _stream()), "stx_style_content_loss")
-    npart = C.c_int()
-    off = L.stx_style_loss_parts(b, c, hw, C.byref(npart))
-    return (wp + off, npart.value, 1.0 / (b * c * c)), coef
+    return _style_loss(b, c, z[0, 0].numel(), target, z.device, weight, diag_alpha, coef,
+                       defer_ws, fin, z=z, z_amax=z_amax, content=content, mse_out=mse_out)
 
 
 def style_loss_from_parts(gparts, nparts, b, c, hw, target, weight=1.0, diag_alpha=0.0,
@@ -860,48 +857,14 @@ def style_loss_from_parts(gparts, nparts, b, c, hw, target, weight=1.0, diag_alp
     and feature-mse values as style_content_loss writes them, from the same launch.
     Returns (deferred LossPart, coef) as style_loss with defer_ws."""
     _req(gparts, "gram partials")
-    _req(target, "target")
     if (mse_parts is None) != (mse_out is None):
         raise ValueError("mse_parts and mse_out go together")
     if mse_parts is not None:
         _req(mse_parts, "mse_parts")
         assert mse_parts.numel() >= 2 * b * nparts and mse_out.numel() >= 3
-    tb = target.numel() == b * c * c and b > 1
-    if not tb and target.numel() != c * c:
-        raise ValueError(f"style target {tuple(target.shape)} cannot expand to ({b},{c},{c})")
-    if coef is None:
-        cp = coef_pitch(c)
-        coef = torch.empty((b, cp, cp), device=gparts.device, dtype=torch.float32)
-    L = lib()
-    need = L.stx_gram_ws(b, c, hw)
-    assert defer_ws is not None and defer_ws.numel() >= need, need
-    wp, wn = defer_ws.data_ptr(), defer_ws.numel()
-    if mse_parts is not None:
-        if fin is not None:
-            check(L.stx_style_content_loss_from_parts_deferred(
-                gparts.data_ptr(), int(nparts), target.data_ptr(), coef.data_ptr(), b, c, hw,
-                int(tb), float(weight), float(diag_alpha), mse_parts.data_ptr(),
-                mse_out.data_ptr(), wp, wn, C.byref(fin.new()), _stream()),
-                "stx_style_content_loss_from_parts_deferred")
-        else:
-            check(L.stx_style_content_loss_from_parts(
-                gparts.data_ptr(), int(nparts), target.data_ptr(), coef.data_ptr(), None, b, c,
-                hw, int(tb), float(weight), float(diag_alpha), mse_parts.data_ptr(),
-                mse_out.data_ptr(), wp, wn, _stream()), "stx_style_content_loss_from_parts")
-    elif fin is not None:
-        check(L.stx_style_loss_from_parts_deferred(gparts.data_ptr(), int(nparts),
-                                                   target.data_ptr(), coef.data_ptr(), b, c, hw,
-                                                   int(tb), float(weight), float(diag_alpha), wp,
-                                                   wn, C.byref(fin.new()), _stream()),
-              "stx_style_loss_from_parts_deferred")
-    else:
-        check(L.stx_style_loss_from_parts(gparts.data_ptr(), int(nparts), target.data_ptr(), None,
-                                          coef.data_ptr(), None, b, c, hw, int(tb), float(weight),
-                                          float(diag_alpha), wp, wn, _stream()),
-              "stx_style_loss_from_parts")
-    npart = C.c_int()
-    off = L.stx_style_loss_parts(b, c, hw, C.byref(npart))
-    return (wp + off, npart.value, 1.0 / (b * c * c)), coef
+    assert defer_ws is not None
+    return _style_loss(b, c, hw, target, gparts.device, weight, diag_alpha, coef, defer_ws, fin,
+                       parts=gparts, nparts=nparts, mse_parts=mse_parts, mse_out=mse_out)
 
 
 def loss_finalize(parts, losses, extra=None, weights=None, total=None):

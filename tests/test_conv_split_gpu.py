@@ -553,7 +553,7 @@ def test_fused_gram_grouped(dev, case):
 @pytest.mark.parametrize("shape", [(1, 128, 256, 256), (2, 128, 24, 40), (1, 64, 32, 32),
                                    (1, 256, 16, 16), (3, 128, 8, 12)])
 def test_style_content_loss(dev, shape):
-    """stx_style_content_loss (the content tap: the style loss with the content, feature
+    """ops.style_content_loss (the content tap: the style loss with the content, feature
     and feature-mse sums in the same pass over z where the Gram kernel allows it)
     equals style_loss + mse(mode=2) run separately."""
     b, c, h, w = shape
@@ -579,6 +579,102 @@ def test_style_content_loss(dev, shape):
     mr = ((zd.clamp(min=0) - cd.clamp(min=0)) ** 2).mean()
     ref = torch.stack([ref0, mr * mr / z.numel(), mr])
     assert rel(m, ref) < 1e-5, (m, ref)
+
+
+# (source, shape, with z_amax) or ("parts", b, c, nparts, with mse_parts): every Gram partial
+# kernel, every fin_groups value (nsplit <= 8: 4, <= 16: 2, else 1) and the padded coef
+FIN_CASES = [
+    ("z", (2, 64, 8, 12), True),        # fp16 split, general kernel
+    ("z", (1, 64, 9, 13), False),       # hw % 4 != 0: scalar fallback
+    ("z", (1, 128, 6, 10), False),      # fp32 MFMA v2
+    ("z", (1, 256, 8, 16), True),       # tri256
+    ("z", (1, 48, 8, 12), False),       # coef pitch 64 > c: the padding is zeroed first
+    ("zc", (2, 128, 8, 16), True),      # content tap, MSE fused into the tri pass
+    ("zc", (1, 64, 8, 12), False),      # content tap, separate MSE pass
+    ("parts", 2, 64, 3, False),
+    ("parts", 2, 64, 12, False),
+    ("parts", 2, 64, 20, False),
+    ("parts", 1, 128, 5, True),         # content tap from a conv epilogue's sums
+]
+_fin_immediate = {}
+
+
+def _fin_case(dev, i, fin=None):
+    """Case i of FIN_CASES through its public op, immediate (fin None) or deferred into
+    fin: (coef, deferred loss part, mse_out or None, tensors to keep until the flush)."""
+    case, L, seed = FIN_CASES[i], N.lib(), 700 + 10 * i
+    m = torch.full((3,), float("nan"), device=dev)
+    if case[0] == "parts":
+        _, b, c, nparts, with_mse = case
+        hw, U = 96, 3 if c == 128 else 1
+        parts = rnd(b * U * nparts * 4096, dev=dev, seed=seed, scale=2, shift=-1)
+        t = rnd(c, c, dev=dev, seed=seed + 1, scale=0.02)
+        mp = rnd(2 * b * nparts, dev=dev, seed=seed + 2) if with_mse else None
+        ws = torch.empty(L.stx_gram_ws(b, c, hw), device=dev, dtype=torch.uint8)
+        lp, coef = ops.style_loss_from_parts(parts, nparts, b, c, hw, t, weight=3.0,
+                                             diag_alpha=0.5, defer_ws=ws, fin=fin, mse_parts=mp,
+                                             mse_out=m if with_mse else None)
+        return coef, lp, (m if with_mse else None), (parts, t, mp, ws)
+    kind, (b, c, h, w), with_amax = case
+    z = rnd(b, c, h, w, dev=dev, seed=seed, scale=2, shift=-1)
+    t = rnd(b, c, c, dev=dev, seed=seed + 1, scale=0.02)
+    am = ops.amax(z) if with_amax else None
+    if kind == "zc":
+        cz = rnd(b, c, h, w, dev=dev, seed=seed + 2, scale=2, shift=-1)
+        ws = torch.empty(L.stx_style_content_ws(b, c, h * w), device=dev, dtype=torch.uint8)
+        lp, coef = ops.style_content_loss(z, t, cz, m, weight=3.0, diag_alpha=0.5, z_amax=am,
+                                          defer_ws=ws, fin=fin)
+        return coef, lp, m, (z, t, am, cz, ws)
+    ws = torch.empty(L.stx_gram_ws(b, c, h * w), device=dev, dtype=torch.uint8)
+    lp, coef = ops.style_loss(z, t, weight=3.0, diag_alpha=0.5, z_amax=am, defer_ws=ws, fin=fin)
+    return coef, lp, None, (z, t, am, ws)
+
+
+def _fin_results(dev, coef, lp, m):
+    loss = torch.zeros(1, device=dev)
+    ops.loss_finalize([lp], loss)
+    torch.cuda.synchronize()
+    return coef, loss, m
+
+
+def _fin_reference(dev, i):
+    if i not in _fin_immediate:
+        coef, lp, m, _ = _fin_case(dev, i)
+        _fin_immediate[i] = _fin_results(dev, coef, lp, m)
+    return _fin_immediate[i]
+
+
+def _fin_assert_same(got, want, i):
+    for g, w in zip(got, want):
+        assert (g is None) == (w is None), FIN_CASES[i]
+        if g is not None:
+            assert not torch.isnan(w).any() and torch.equal(g, w), FIN_CASES[i]
+
+
+@pytest.mark.parametrize("i", range(len(FIN_CASES)))
+def test_deferred_finalize_bit_identical(dev, i):
+    """A finalize deferred into stx_gram_finalize_batch gives the bits of the immediate
+    call (include/stx.h): coef, the loss and mse_out, for features and for precomputed
+    partials, with and without the content companion."""
+    want = _fin_reference(dev, i)
+    fin = ops.FinalizeBatch()
+    coef, lp, m, keep = _fin_case(dev, i, fin)
+    assert len(fin.jobs) == 1
+    fin.flush()
+    _fin_assert_same(_fin_results(dev, coef, lp, m), want, i)
+
+
+def test_deferred_finalize_batched_bit_identical(dev):
+    """The same with up to STX_FIN_MAX jobs of different shapes in one flush (the batch
+    kernel's block-range decode)."""
+    for lo in range(0, len(FIN_CASES), N.STX_FIN_MAX):
+        idx = range(lo, min(lo + N.STX_FIN_MAX, len(FIN_CASES)))
+        fin = ops.FinalizeBatch()
+        runs = [_fin_case(dev, i, fin) for i in idx]
+        assert len(fin.jobs) == len(idx)
+        fin.flush()
+        for i, (coef, lp, m, keep) in zip(idx, runs):
+            _fin_assert_same(_fin_results(dev, coef, lp, m), _fin_reference(dev, i), i)
 
 
 @pytest.mark.parametrize("shape", [(2, 64, 20, 70), (1, 128, 34, 64), (1, 256, 16, 16),

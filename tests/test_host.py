@@ -35,10 +35,13 @@ def test_struct_mirrors_match_the_library():
     way round, fails here instead of shifting fields on the GPU."""
     import ctypes as C
     from styletransfer_amd import _native as N
-    out = (C.c_longlong * 12)()
-    assert N.lib().stx_abi_layout(C.cast(out, C.c_void_p), 12) == 12
     mirrors = [(N.ConvParams, "unpool_out"), (N.WprepJob, "pad_"), (N.LossParts, "k"),
-               (N.GramFinJob, "coef_amax"), (N.PGradJob, "pad_"), (N.ImageMeta, "tmp_offset")]
+               (N.GramFinJob, "coef_amax"), (N.PGradJob, "pad_"), (N.ImageMeta, "tmp_offset"),
+               (N.CinJob, "accumulate"), (N.StyleLossParams, "defer")]
+    count = N.lib().stx_abi_layout(None, 0)
+    assert count == 2 * len(mirrors)
+    out = (C.c_longlong * count)()
+    assert N.lib().stx_abi_layout(C.cast(out, C.c_void_p), count) == count
     for i, (S, last) in enumerate(mirrors):
         assert S._fields_[-1][0] == last, S
         assert (C.sizeof(S), getattr(S, last).offset) == (out[2 * i], out[2 * i + 1]), S
@@ -81,6 +84,43 @@ def test_pool_sum_contract_rejected():
     p.relu_out, p.ho, p.wo, p.hv, p.wv, p.h, p.w = 0, 63, 63, 63, 63, 63, 63  # odd output
     rc = cp.stx_conv2d(C.byref(p), op)
     assert rc == 1001 and b"pool_sum" in cp.stx_last_error_string()
+
+
+def test_style_loss_malformed_params_rejected():
+    """stx_style_loss refuses a malformed stx_style_loss_params before any launch (no GPU
+    is present here and the pointers are fake): invalid, or the workspace code."""
+    from styletransfer_amd import _native as N
+    import ctypes as C
+    L = N.lib()
+    b, c, hw = 2, 64, 96
+    gram_ws, content_ws = L.stx_gram_ws(b, c, hw), L.stx_style_content_ws(b, c, hw)
+    assert 0 < gram_ws < content_ws
+    job = N.GramFinJob()
+
+    def refused(code, **kw):
+        f = dict(target=16, coef=32, b=b, c=c, hw=hw, weight=1.0, ws=4096, ws_bytes=content_ws)
+        f.update(kw)
+        rc = L.stx_style_loss(C.byref(N.StyleLossParams(**f)), None)
+        msg = L.stx_last_error_string()
+        assert rc == code and b"stx_style_loss" in msg, (kw, rc, msg)
+
+    rc = L.stx_style_loss(C.byref(N.StyleLossParams()), None)  # all zero
+    assert rc == 1001 and b"stx_style_loss" in L.stx_last_error_string()
+    refused(1001, z=48, parts=64, nparts=3)                     # both sources
+    refused(1001)                                               # neither
+    refused(1001, z=48, target=None)
+    refused(1001, parts=64, nparts=3, c=96)
+    refused(1001, parts=64, nparts=0)
+    refused(1001, z=48, content=80)                             # content without mse_out
+    refused(1001, z=48, mse_out=96)                             # mse_out without content
+    refused(1001, z=48, mse_parts=80, mse_out=96)               # mse_parts with z
+    refused(1001, parts=64, nparts=3, content=80, mse_out=96)   # content with parts
+    refused(1001, z=48, loss=112, defer=C.pointer(job))         # defer excludes loss
+    refused(1002, z=48, ws_bytes=gram_ws - 1)
+    refused(1002, parts=64, nparts=3, ws_bytes=gram_ws - 1)
+    refused(1002, z=48, ws=None)
+    refused(1002, z=48, content=80, mse_out=96, ws_bytes=gram_ws)  # < stx_style_content_ws
+    assert bytes(job) == bytes(N.GramFinJob())                  # a refused call writes no job
 
 
 def test_phase2_contract_rejected():

@@ -15,10 +15,13 @@ E_INVALID = 1001
 
 
 def test_cin_job_mirror_matches_the_library():
-    out = (C.c_longlong * 2)()
-    assert N.lib().stx_cin_abi_layout(C.cast(out, C.c_void_p), 2) == 2
+    mirrors = 8  # stx_abi_layout's table (include/stx.h); stx_cin_job is its seventh entry
+    count = N.lib().stx_abi_layout(None, 0)
+    assert count == 2 * mirrors
+    out = (C.c_longlong * count)()
+    assert N.lib().stx_abi_layout(C.cast(out, C.c_void_p), count) == count
     assert N.CinJob._fields_[-1][0] == "accumulate"
-    assert (C.sizeof(N.CinJob), N.CinJob.accumulate.offset) == (out[0], out[1])
+    assert (C.sizeof(N.CinJob), N.CinJob.accumulate.offset) == (out[12], out[13])
 
 
 def _job(**kw):
