@@ -193,8 +193,8 @@ const char* stx_last_error_string(void);
  * stx_instnorm_bwd's second argument is beta, not y; 7: stx_conv_params.unpool_out;
  * 9: the guided Gram entry points; 10: stx_style_loss takes stx_style_loss_params).  The
  * revision moves only when an existing entry point or struct changes meaning; entry
- * points that are merely added (the colour control pair below) do not bump it -- a
- * binding finds a missing symbol at load. */
+ * points that are merely added (the colour control pair, the flow entry points below) do
+ * not bump it -- a binding finds a missing symbol at load. */
 #define STX_ABI_VERSION 10
 int stx_abi_version(void);
 
@@ -675,6 +675,55 @@ int stx_temporal_loss(const float* y, const float* y_old, const float* x, const 
 int stx_temporal_loss_bwd(const float* y, const float* y_old, long long n, const float* fwd,
                           float weight, const float* g_dev, float* grad, int accumulate,
                           void* stream);
+
+/* Temporal consistency of optimisation-based video transfer (Ruder, Dosovitskiy & Brox 2016,
+ * "Artistic Style Transfer for Videos").  Images and flows are NCHW fp32 with h, w >= 2; a
+ * flow is [n][2][h][w], channel 0 the column displacement dx, channel 1 the row
+ * displacement dy, in pixels.
+ *
+ * stx_flow_warp: out[b][k][i][j] = src[b][k] sampled bilinearly at y = i + flow[b][1][i][j],
+ * x = j + flow[b][0][i][j] (fp32, one rounding each).
+ *   valid = 0 <= y <= h-1 and 0 <= x <= w-1, compared on the fp32 coordinates as computed:
+ *           a NaN or infinite coordinate is invalid.
+ *   y0 = min(floor(y), h-2), y1 = y0 + 1, fy = y - y0 (likewise x); the taps' weights are
+ *   (1-fy)(1-fx), (1-fy)fx, fy(1-fx), fy fx, computed once per pixel and reused over the c
+ *   channels; the value is w00 a00 + w01 a01 + w10 a10 + w11 a11 as one product and three
+ *   fmaf in that order (seven roundings at most: three on a weight, four in the sum).
+ *   All four taps enter the sum, so a NaN tap makes the pixel NaN even under a zero weight.
+ *   An invalid pixel reads no tap: out = fill[b][k][i][j] if fill is given, else +0.
+ *   valid (optional) [n][h][w] receives 1.0f / 0.0f.  out must not overlap src; n <= 65535.
+ *
+ * stx_flow_consistency: cmask [n][h][w] = 1.0f where the pixel of frame t has a consistent
+ * source in frame t-1, else 0.0f.  With w^ = bwd at the pixel and w~ = fwd warped by bwd
+ * (stx_flow_warp's arithmetic), the pixel is
+ *   occluded  if |w~ + w^|^2 > 0.01 (|w~|^2 + |w^|^2) + 0.5
+ *   boundary  if |grad u^|^2 + |grad v^|^2 > 0.01 |w^|^2 + 0.002
+ * (grad: central difference halved in the interior, one-sided and unhalved in the first
+ * and last row and column), and cmask = valid and not occluded and not boundary.  A NaN on
+ * either side of a comparison makes it false: a NaN in bwd at the pixel makes it invalid
+ * (0), one in a neighbour's bwd or in a tap of fwd only silences the test it enters.
+ *
+ * stx_masked_mse: x, ref [n][c][hw], mask [n][hw] shared by the c channels:
+ *   out[0] = weight / (n c hw) * sum over mask != 0 of (x - ref)^2
+ *   grad (optional) = or += 2 weight / (n c hw) * (x - ref) where mask != 0
+ * One streaming pass (512 blocks, fixed assignment) and a one-block finalize in a fixed
+ * order: bit-reproducible.  The finalize also does *add_to += out[0] when add_to is given.
+ * The mask selects: where mask == 0 nothing of x or ref reaches the loss or the gradient
+ * (not a NaN either); grad is then written +0, or with accumulate left as it is, bit for
+ * bit.  A NaN in the mask selects the pixel.  A NaN in x or ref under a set mask makes the
+ * loss and that gradient element NaN.  Bases that are 16-byte aligned with hw % 4 == 0
+ * take float4 accesses, anything else the scalar loop: the same values up to the order of
+ * the per-thread sums.  n c hw < 2^31.
+ *
+ * None of the three allocates or synchronises; arguments are checked before any launch. */
+int stx_flow_warp(const float* src, const float* flow, const float* fill, float* out,
+                  float* valid, int n, int c, int h, int w, void* stream);
+int stx_flow_consistency(const float* fwd, const float* bwd, float* cmask, int n, int h, int w,
+                         void* stream);
+size_t stx_masked_mse_ws(void);
+int stx_masked_mse(const float* x, const float* ref, const float* mask, int n, int c, int hw,
+                   float weight, float* out, float* add_to, float* grad, int accumulate,
+                   void* ws, size_t ws_bytes, void* stream);
 
 /* Image conditioning (img_utils.image_loader_transform, stransfer/img_utils.py:13-44)
  * of a batch of decoded 8-bit RGB images on the GPU: centre crop, Pillow-exact

@@ -1,7 +1,7 @@
 """`python -m stransfer` command groups (mirror of stransfer/clis/__init__.py)."""
 import click
 
-from . import fast_st, gatys_guided, gatys_st, video_st
+from . import fast_st, gatys_guided, gatys_st, gatys_video, video_st
 
 
 @click.group(commands={
@@ -9,6 +9,7 @@ from . import fast_st, gatys_guided, gatys_st, video_st
     "fast_st": fast_st.fast_st,
     "gatys_st": gatys_st.gatys_st,
     "gatys_guided": gatys_guided.gatys_guided,
+    "gatys_video": gatys_video.gatys_video,
 })
 def cli():
     """Style Transfer (MI355X)"""

@@ -1,0 +1,77 @@
+"""`gatys_video` command: temporally consistent Gatys transfer of a clip (Ruder, Dosovitskiy
+& Brox 2016, "Artistic Style Transfer for Videos"): every frame is optimised from the
+previous result warped along the optical flow, under a consistency-masked temporal loss."""
+import os
+
+import click
+
+from .. import c_logging, constants
+from .gatys_st import parse_layer_weights
+
+LOGGER = c_logging.get_logger()
+
+
+def parse_flow(ctx, param, value):
+    """--flow static | FLOWS.npz (an existing file under the project root)."""
+    if value == "static":
+        return value
+    path = os.path.join(constants.PROJECT_ROOT_PATH, value)
+    if not os.path.isfile(path):
+        raise click.BadParameter(f"'{value}': 'static' or an .npz file with 'forward' and "
+                                 "'backward' flows expected", param_hint="--flow")
+    return path
+
+
+@click.command()
+@click.argument("frames-path")
+@click.argument("style-image-path")
+@click.option("--flow", required=True, callback=parse_flow, metavar="FLOWS.npz|static",
+              help="Optical flows between the conditioned frames: an .npz with 'forward' and "
+                   "'backward', each [T-1, 2, S, S] float32 in pixels at the working "
+                   "resolution (channel 0 = columns, 1 = rows); static = a fixed camera")
+@click.option("-s", "--steps", default=100, type=click.IntRange(min=0),
+              help="Iterations per frame after the first")
+@click.option("--first-steps", default=None, type=click.IntRange(min=0),
+              help="Iterations of the first frame (default: -s)")
+@click.option("-tw", "--temporal-weight", default=None, type=float,
+              help="The weight of the temporal loss (default 200: Ruder et al.'s ratio to a "
+                   "content weight of 1)")
+@click.option("-cw", "--content-weight", default=1,
+              help="The weight we will assign to the content loss during the optimization")
+@click.option("-sw", "--style-weight", default=100_000,
+              help="The weight we will assign to the style loss during the optimization")
+@click.option("--optimizer", type=click.Choice(["adam", "lbfgs"]), default="adam",
+              help="adam = one captured engine moved from frame to frame; lbfgs = an L-BFGS "
+                   "engine per frame (-s counts its outer steps)")
+@click.option("--layer-weights", callback=parse_layer_weights, default=None,
+              metavar="A,B,C,D,E",
+              help="Multipliers of the style weight per style tap, conv1_1 .. conv3_1")
+@click.option("-o", "--out-dir", default="results/gatys_video/",
+              help="Where the stylised frames 0.png, 1.png, ... are written")
+def gatys_video(frames_path, style_image_path, flow, steps, first_steps, temporal_weight,
+                content_weight, style_weight, optimizer, layer_weights, out_dir):
+    """Gatys style transfer of a clip, consistent from frame to frame.
+    FRAMES_PATH: a directory of frames or a .npy array [T, H, W, 3] uint8."""
+    from .. import img_utils, network, video
+    root = constants.PROJECT_ROOT_PATH
+    src = os.path.join(root, frames_path)
+    frames = list(video.iterate_frames(src))
+    if not frames:
+        raise click.UsageError(f"no frames in {frames_path}")
+    flows = flow
+    if flow != "static":
+        try:
+            flows = video.load_flows(flow, len(frames), frames[0].shape[-1])
+        except ValueError as e:
+            raise click.UsageError(str(e)) from None
+    style_image = img_utils.image_loader(os.path.join(root, style_image_path))
+    net = network.StyleNetwork(style_image)
+    out_dir = os.path.join(root, out_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    out = net.train_gatys_video(frames, style_image, flows, steps=steps, first_steps=first_steps,
+                                temporal_weight=temporal_weight, optimizer=optimizer,
+                                style_weight=style_weight, content_weight=content_weight,
+                                style_layer_weights=layer_weights)
+    for i, y in enumerate(out):
+        img_utils.imshow(y[0], path=os.path.join(out_dir, f"{i}.png"))
+    LOGGER.info("Done! %d stylised frames have been saved to: %s", len(frames), out_dir)

@@ -424,6 +424,20 @@ class StyleNetwork(nn.Module):
         eng.run(steps, graph=graph)
         return eng.x
 
+    def train_gatys_video(self, frames, style_image, flows, steps=100, first_steps=None,
+                          temporal_weight=None, optimizer="adam", style_weight=100_000,
+                          content_weight=1, style_layer_weights=None):
+        """Temporally consistent Gatys transfer of a clip (video.gatys_video; Ruder et al.
+        2016): an iterator of stylised frames.  frames: conditioned frames [1, 3, h, w];
+        flows: "static" or (forward, backward) at the frames' resolution."""
+        from . import video
+        tw = video.DEFAULT_TEMPORAL_WEIGHT if temporal_weight is None else temporal_weight
+        return video.gatys_video(self.features(), frames, _dev(style_image), flows, steps,
+                                 first_steps=first_steps, temporal_weight=tw,
+                                 optimizer=optimizer, style_weight=style_weight,
+                                 content_weight=content_weight,
+                                 style_layer_weights=style_layer_weights)
+
     def train_gatys_multiscale(self, style_image, content_image, sizes, steps,
                                optimizer="lbfgs", style_weight=100_000, content_weight=1,
                                style_layer_weights=None) -> torch.Tensor:

@@ -23,7 +23,8 @@ __all__ = [
     "bias_grad", "gram", "style_loss", "gram_bwd", "guided_style_loss", "guided_gram_bwd", "mse", "diff_scale", "loss_combine",
     "maxpool2x2", "maxpool2x2_bwd", "relupool_bwd", "relu", "relu_bwd", "adam_step",
     "instnorm_fwd", "instnorm_bwd", "cin_mix", "upsample2x", "upsample2x_bwd", "tv_loss",
-    "temporal_loss", "temporal_loss_bwd", "color_stats", "color_affine", "resample_plan",
+    "temporal_loss", "temporal_loss_bwd", "flow_warp", "flow_consistency", "masked_mse",
+    "color_stats", "color_affine", "resample_plan",
     "resample2d",
 ]
 
@@ -1253,6 +1254,90 @@ def temporal_loss_bwd(y, y_old, fwd, weight=1.0, g=None, grad=None, accumulate=F
                                       float(weight), _p(g), grad.data_ptr(), int(accumulate),
                                       _stream()), "stx_temporal_loss_bwd")
     return grad
+
+
+# --------------------------------------------------------- flow-warped temporal consistency
+def _flow2(t, name, like=None):
+    _req(t, name)
+    if t.dim() != 4 or t.shape[1] != 2 or min(t.shape[2:]) < 2:
+        raise N.NativeError(f"{name}: a flow [n, 2, h, w] with h, w >= 2 required "
+                            f"(got {tuple(t.shape)})")
+    if like is not None and (t.shape[0], *t.shape[2:]) != (like.shape[0], *like.shape[2:]):
+        raise N.NativeError(f"{name}: {tuple(t.shape)} does not match {tuple(like.shape)}")
+    return t
+
+
+def flow_warp(src, flow, fill=None, out=None, want_valid=False):
+    """src [n, c, h, w] sampled bilinearly at (i + flow[:, 1], j + flow[:, 0]) (stx_flow_warp):
+    a pixel whose source lies outside the image takes fill's value (0 without fill).
+    want_valid: True returns (out, valid), valid [n, h, w] of 1.0 / 0.0; a tensor is filled
+    and returned in that place.  out must not alias src."""
+    _req(src, "src")
+    if src.dim() != 4:
+        raise N.NativeError(f"src: [n, c, h, w] required (got {tuple(src.shape)})")
+    _flow2(flow, "flow", src)
+    n, c, h, w = src.shape
+    if out is None:
+        out = torch.empty_like(src)
+    for t, nm in ((fill, "fill"), (out, "out")):
+        if t is not None:
+            _req(t, nm)
+            assert t.shape == src.shape, (nm, t.shape, src.shape)
+    valid = None
+    if want_valid is True:
+        valid = torch.empty((n, h, w), device=src.device, dtype=torch.float32)
+    elif want_valid is not False and want_valid is not None:
+        valid = _req(want_valid, "valid")
+        assert valid.numel() == n * h * w, (valid.shape, src.shape)
+    check(lib().stx_flow_warp(src.data_ptr(), flow.data_ptr(), _p(fill), out.data_ptr(),
+                              _p(valid), n, c, h, w, _stream()), "stx_flow_warp")
+    return out if valid is None else (out, valid)
+
+
+def flow_consistency(fwd, bwd, out=None):
+    """The consistency mask [n, h, w] (1.0 / 0.0) of frame t given fwd (t-1 -> t) and bwd
+    (t -> t-1): 0 where the backward flow leaves the image, at disocclusions and at motion
+    boundaries (stx_flow_consistency; Ruder et al. 2016, eq. 5 and 6)."""
+    _flow2(bwd, "bwd")
+    _flow2(fwd, "fwd", bwd)
+    n, _, h, w = bwd.shape
+    if out is None:
+        out = torch.empty((n, h, w), device=bwd.device, dtype=torch.float32)
+    _req(out, "out")
+    assert out.numel() == n * h * w, (out.shape, bwd.shape)
+    check(lib().stx_flow_consistency(fwd.data_ptr(), bwd.data_ptr(), out.data_ptr(), n, h, w,
+                                     _stream()), "stx_flow_consistency")
+    return out
+
+
+def masked_mse(x, ref, mask, weight, out=None, add_to=None, grad=None, accumulate=False):
+    """out[0] = weight / x.numel() * sum over mask != 0 of (x - ref)^2 (stx_masked_mse), x and
+    ref [n, c, h, w], mask [n, h, w] shared by the channels.  add_to: a device scalar that
+    receives += the loss; grad: written, or with accumulate added to, 2 weight / x.numel() *
+    (x - ref) under the mask (a masked-out element is 0, or left as it is)."""
+    _req(x, "x")
+    _req(ref, "ref")
+    _req(mask, "mask")
+    if x.dim() != 4 or ref.shape != x.shape:
+        raise N.NativeError(f"x, ref: equal [n, c, h, w] required (got {tuple(x.shape)}, "
+                            f"{tuple(ref.shape)})")
+    n, c, h, w = x.shape
+    if mask.numel() != n * h * w:
+        raise N.NativeError(f"mask: [n, h, w] of x {tuple(x.shape)} required "
+                            f"(got {tuple(mask.shape)})")
+    if out is None:
+        out = torch.empty(1, device=x.device, dtype=torch.float32)
+    for t, nm in ((out, "out"), (add_to, "add_to"), (grad, "grad")):
+        if t is not None:
+            _req(t, nm)
+    if grad is not None:
+        assert grad.shape == x.shape, (grad.shape, x.shape)
+    L = lib()
+    wp, wn = _scratch().get(L.stx_masked_mse_ws(), x.device)
+    check(L.stx_masked_mse(x.data_ptr(), ref.data_ptr(), mask.data_ptr(), n, c, h * w,
+                           float(weight), out.data_ptr(), _p(add_to), _p(grad),
+                           int(bool(accumulate)), wp, wn, _stream()), "stx_masked_mse")
+    return out
 
 
 # ---------------------------------------------------------------------- colour control

@@ -510,6 +510,32 @@ def content_target(feat: VGGFeatures, content, out=None, amax=None):
         feat.forward(content.contiguous(), 4, [None, None, None, out], amax=amax)[3]
 
 
+def _own_temporal(eng, temporal):
+    """temporal = (ref, mask, weight) of a Gatys engine (None: no term, no buffer): the
+    engine's own static copies of ref [1, 3, h, w] (the previous result warped onto this
+    frame) and mask [1, h, w] (ops.flow_consistency), and the device scalar of the term."""
+    eng.temporal = eng.tloss = None
+    if temporal is None:
+        return
+    ref, mask, weight = temporal
+    x = eng.x
+    if ref.numel() != x.numel() or mask.numel() != x.numel() // x.shape[1]:
+        raise ValueError(f"temporal: ref {tuple(ref.shape)} / mask {tuple(mask.shape)} do not "
+                         f"match the canvas {tuple(x.shape)}")
+    ref = ref.to(x.device, torch.float32).reshape(x.shape).clone().contiguous()
+    mask = mask.to(x.device, torch.float32).reshape(x.shape[0], *x.shape[2:]).clone().contiguous()
+    eng.temporal = (ref, mask, float(weight))
+    eng.tloss = torch.zeros(1, device=x.device, dtype=torch.float32)
+
+
+def _temporal_term(eng):
+    """total += weight / x.numel() * sum mask (x - ref)^2 and its gradient onto grad: one
+    streaming launch and a one-block finalize after loss_backward."""
+    ref, mask, weight = eng.temporal
+    ops.masked_mse(eng.x, ref, mask, weight, out=eng.tloss, add_to=eng.total, grad=eng.grad,
+                   accumulate=True)
+
+
 class GatysEngine:
     """One Gatys iteration = forward + backward + Adam on the image, as a single
     hipGraph replay (BASELINE.json config 2):
@@ -522,7 +548,7 @@ class GatysEngine:
 
     def __init__(self, feat: VGGFeatures, style_image, content_image, style_weight=100_000,
                  content_weight=1, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, init=None,
-                 targets=None, style_layer_weights=None):
+                 targets=None, style_layer_weights=None, temporal=None):
         dev = feat.device
         self.feat = feat
         if targets is None:
@@ -532,6 +558,7 @@ class GatysEngine:
         self.c4 = content_target(feat, self.content).clone()
         src = self.content if init is None else init.to(dev, torch.float32)
         self.x = src.clone().contiguous()
+        _own_temporal(self, temporal)
         self.grad = torch.zeros_like(self.x)
         self.m = torch.zeros_like(self.x)
         self.v = torch.zeros_like(self.x)
@@ -552,10 +579,38 @@ class GatysEngine:
                      folded_weights=(self.sw, self.cw), total=self.total)
         loss_backward(self.feat, self.st, dx=self.grad, feature_grad=False,
                       scratch=self.scratch)
+        if self.temporal is not None:
+            _temporal_term(self)
         # the Adam launch also zeroes the amax groups for the next iteration's forward
         ops.adam_step(self.x, self.grad, self.m, self.v, self.step_dev, self.adam_ws, self.lr,
                       self.betas[0], self.betas[1], self.eps, clear=self.st.amax)
         self.st.amax_cleared = True
+
+    def retarget(self, content, init=None, temporal_ref=None, temporal_mask=None):
+        """Move the engine to the next frame of a clip in place, keeping a captured graph:
+        every buffer the graph reads or writes stays where it is.  The content target is
+        recomputed into c4; with a temporal term its ref and mask (each kept as it is when
+        None) are copied into the engine's static copies; x restarts from init (the content
+        when None) and Adam from step 0 with zero moments.  The iteration reads the content
+        only through c4, so `content` is held as the constructor holds its image -- by
+        reference, never written."""
+        content = content.to(self.x.device, torch.float32).contiguous()
+        if content.shape != self.content.shape:
+            raise ValueError(f"retarget: content {tuple(content.shape)}, the engine holds "
+                             f"{tuple(self.content.shape)}")
+        if self.temporal is None and (temporal_ref is not None or temporal_mask is not None):
+            raise ValueError("retarget: the engine was built without a temporal term")
+        self.content = content
+        content_target(self.feat, self.content, out=self.c4)
+        if temporal_ref is not None:
+            self.temporal[0].copy_(temporal_ref.reshape(self.x.shape))
+        if temporal_mask is not None:
+            self.temporal[1].copy_(temporal_mask.reshape(self.temporal[1].shape))
+        self.x.copy_(self.content if init is None else init.reshape(self.x.shape))
+        self.m.zero_()
+        self.v.zero_()
+        self.step_dev.zero_()
+        return self
 
     def capture(self, warmup=2):
         """Capture one iteration into a hipGraph (after `warmup` eager iterations,
@@ -617,7 +672,7 @@ class GatysLBFGS:
 
     def __init__(self, feat: VGGFeatures, style_image, content_image, style_weight=100_000,
                  content_weight=1, targets=None, init=None, style_layer_weights=None,
-                 **lbfgs_kw):
+                 temporal=None, **lbfgs_kw):
         from .optim import LBFGS
         dev = feat.device
         self.feat = feat
@@ -628,6 +683,7 @@ class GatysLBFGS:
         self.c4 = content_target(feat, self.content).clone()
         src = self.content if init is None else init.to(dev, torch.float32)
         self.x = src.clone().contiguous()
+        _own_temporal(self, temporal)
         self.grad = torch.zeros_like(self.x)
         self.sw, self.cw = _folded_style(style_weight, style_layer_weights), float(content_weight)
         self.total = torch.zeros((), device=dev, dtype=torch.float32)
@@ -644,6 +700,8 @@ class GatysLBFGS:
                      folded_weights=(self.sw, self.cw), total=self.total)
         loss_backward(self.feat, self.st, dx=self.grad, feature_grad=False,
                       scratch=self.scratch)
+        if self.temporal is not None:
+            _temporal_term(self)
         # the statistics launch also zeroes the amax groups for the next forward
         self.opt.grad_stats(self.grad.view(-1), self.total.view(1), clear=self.st.amax)
         self.st.amax_cleared = True

@@ -8,6 +8,10 @@ frame along channels (`torch.cat([frame, old], dim=1)`, the first frame with
 itself) and run through the 6-channel ImageTransformNet; the output becomes the
 next frame's `old`.  `get_temporal_loss` (:885-903) is ||dy|| / (||dx|| + 1).
 
+`gatys_video` is the optimisation-based counterpart (Ruder, Dosovitskiy & Brox 2016):
+the fused Gatys iteration per frame, started from the previous result warped along the
+optical flow and tied to it by a consistency-masked loss.
+
 `FrameEngine` makes one frame one hipGraph replay: the frame is copied into
 channels 0-2 of a static [1, 6, H, W] input whose channels 3-5 hold the previous
 output, the ITN forward runs on the HIP kernels, the output is copied back into
@@ -218,3 +222,103 @@ def process_video(net, video_path, style_name="nsp", working_dir="workdir/", out
         writer.append_data(np.array(Image.open(os.path.join(working_dir, nm))))
     writer.close()
     return final
+
+
+# --------------------------------------------------- temporally consistent Gatys video
+DEFAULT_TEMPORAL_WEIGHT = 200.0  # Ruder et al.: temporal 200 to content 1
+
+
+def load_flows(path, n_frames, size):
+    """(forward, backward) of an .npz: float32 arrays [n_frames - 1, 2, size, size] at the
+    working resolution -- the flows between the conditioned frames (after centre crop and
+    resize), channel 0 the column displacement, channel 1 the row displacement, in pixels.
+    forward[t-1] maps frame t-1 onto frame t, backward[t-1] frame t onto frame t-1.
+    ValueError names what is wrong with a file that does not fit."""
+    with np.load(path, allow_pickle=False) as z:
+        out = []
+        for key in ("forward", "backward"):
+            if key not in z.files:
+                raise ValueError(f"{path}: no '{key}' array (found {sorted(z.files)})")
+            a = z[key]
+            if a.dtype != np.float32:
+                raise ValueError(f"{path}: '{key}' is {a.dtype}, float32 expected")
+            if a.ndim != 4 or a.shape[1:] != (2, size, size):
+                raise ValueError(f"{path}: '{key}' has shape {a.shape}, expected "
+                                 f"[T-1, 2, {size}, {size}] (flows at the working resolution)")
+            if a.shape[0] != n_frames - 1:
+                raise ValueError(f"{path}: '{key}' holds {a.shape[0]} flows, the clip's "
+                                 f"{n_frames} frames need {n_frames - 1}")
+            bad = int(a.size - np.isfinite(a).sum())
+            if bad:
+                raise ValueError(f"{path}: '{key}' holds {bad} non-finite values "
+                                 f"({bad / a.size:.2%} of it)")
+            out.append(np.ascontiguousarray(a))
+    return out[0], out[1]
+
+
+def gatys_video(feat, frames, style_image, flows, steps, first_steps=None,
+                temporal_weight=DEFAULT_TEMPORAL_WEIGHT, optimizer="adam", style_weight=100_000,
+                content_weight=1, style_layer_weights=None, lr=1e-3) -> Iterator[torch.Tensor]:
+    """Stylised frames [1, 3, h, w] of a clip, one Gatys optimisation per frame (Ruder,
+    Dosovitskiy & Brox 2016, short-term consistency).  frames: conditioned frames, as
+    iterate_frames yields them; flows: "static" (a fixed camera: zero flow both ways) or
+    (forward, backward), each [T-1, 2, h, w] (load_flows).  Frame 0 runs first_steps
+    (default steps) from the content frame.  Frame t >= 1 starts from the previous result
+    warped along backward[t-1] (the frame itself where the warp leaves the image) and adds
+
+        temporal_weight / (3 h w) * sum c (x - warp)^2,   c = ops.flow_consistency,
+
+    to the Gatys loss.  optimizer "adam": one engine, captured once and moved from frame to
+    frame (GatysEngine.retarget), steps = iterations; "lbfgs": a GatysLBFGS per frame,
+    steps = outer steps."""
+    from . import vgg as V
+    if optimizer not in ("adam", "lbfgs"):
+        raise ValueError(f"optimizer {optimizer!r}: 'adam' or 'lbfgs'")
+    dev = feat.device
+    static = isinstance(flows, str)
+    if static and flows != "static":
+        raise ValueError(f"flows {flows!r}: 'static' or (forward, backward)")
+    first_steps = steps if first_steps is None else first_steps
+    targets = feat.style_targets(style_image.to(dev, torch.float32))
+    kw = dict(style_weight=style_weight, content_weight=content_weight, targets=targets,
+              style_layer_weights=style_layer_weights)
+    eng = prev = omega = init = cmask = zero = None
+    for t, frame in enumerate(frames):
+        frame = frame.to(dev, torch.float32).contiguous()
+        if t == 0:
+            n, _, h, w = frame.shape
+            prev, omega, init = (torch.empty_like(frame) for _ in range(3))
+            cmask = torch.zeros((n, h, w), device=dev, dtype=torch.float32)
+            zero = torch.zeros((n, 2, h, w), device=dev, dtype=torch.float32)
+            omega.copy_(frame)  # frame 0: an all-zero mask, the term is exactly 0
+            if optimizer == "adam":
+                eng = V.GatysEngine(feat, None, frame, lr=lr,
+                                    temporal=(omega, cmask, temporal_weight), **kw)
+                eng.run(first_steps)
+            else:
+                eng = V.GatysLBFGS(feat, None, frame, **kw)
+                eng.run(first_steps)
+        else:
+            if static:
+                fwd = bwd = zero
+            else:
+                if t - 1 >= len(flows[0]):
+                    raise ValueError(f"frame {t}: only {len(flows[0])} flows given")
+                fwd, bwd = (torch.as_tensor(f[t - 1]).to(dev, torch.float32)
+                            .reshape(zero.shape).contiguous() for f in flows)
+            ops.flow_consistency(fwd, bwd, out=cmask)
+            ops.flow_warp(prev, bwd, out=omega)
+            ops.flow_warp(prev, bwd, fill=frame, out=init)
+            if optimizer == "adam":
+                eng.retarget(frame, init=init, temporal_ref=omega, temporal_mask=cmask)
+                if eng.graph is None:
+                    eng.run(steps)
+                else:
+                    for _ in range(steps):
+                        eng.graph.replay()
+            else:
+                eng = V.GatysLBFGS(feat, None, frame, init=init,
+                                   temporal=(omega, cmask, temporal_weight), **kw)
+                eng.run(steps)
+        prev.copy_(eng.x.detach())
+        yield prev.clone()
