@@ -184,18 +184,19 @@ typedef struct stx_conv_params {
 int stx_version(void);
 /* sizeof and the offset of the last member of each ABI struct, in this order:
  * stx_conv_params, stx_wprep_job, stx_loss_parts, stx_gram_fin_job, stx_in_pgrad_job,
- * stx_image_meta, stx_cin_job, stx_style_loss_params -- two values each, min(n, count)
- * written to out; returns the count.  Bindings check their struct mirrors against it. */
+ * stx_image_meta, stx_cin_job, stx_style_loss_params, stx_wgrad_params -- two values each,
+ * min(n, count) written to out; returns the count.  Bindings check their mirrors against it. */
 int stx_abi_layout(long long* out, int n);
 const char* stx_last_error_string(void);
 /* The ABI revision of this header (STX_ABI_VERSION): a host binding refuses a library of
  * another revision rather than pass arguments whose meaning changed (round 6:
  * stx_instnorm_bwd's second argument is beta, not y; 7: stx_conv_params.unpool_out;
- * 9: the guided Gram entry points; 10: stx_style_loss takes stx_style_loss_params).  The
- * revision moves only when an existing entry point or struct changes meaning; entry
- * points that are merely added (the colour control pair, the flow entry points below) do
- * not bump it -- a binding finds a missing symbol at load. */
-#define STX_ABI_VERSION 10
+ * 9: the guided Gram entry points; 10: stx_style_loss takes stx_style_loss_params; 11:
+ * stx_conv2d_wgrad takes stx_wgrad_params).  The revision moves only when an existing
+ * entry point or struct changes meaning; entry points that are merely added (the colour
+ * control pair, the flow entry points below) do not bump it -- a binding finds a missing
+ * symbol at load. */
+#define STX_ABI_VERSION 11
 int stx_abi_version(void);
 
 /* Padded GEMM dims the conv kernels expect for a (cin, cout, ks) conv. */
@@ -284,42 +285,44 @@ int stx_conv_gram_groups(const stx_conv_params* p);
 int stx_conv2d(const stx_conv_params* p, void* stream);
 
 /* Weight gradient: dw[cout][cin][ks][ks] (+)= sum_{n,oy,ox} dy * xv  (xv = in_mode(x)).
- * Split-K partial slabs in ws (fp32), reduced in fixed order (deterministic).
- * Supported: ks=3 stride 1/2, ks=9 stride 1.  Workspace: stx_conv2d_wgrad_ws(). */
-size_t stx_conv2d_wgrad_ws(int n, int cin, int cout, int ks, int stride, int ho, int wo);
-int stx_conv2d_wgrad(const float* x, const float* dy, float* dw, int accumulate,
-                     int n, int cin, int h, int w, int cout, int ks, int stride, int pad,
-                     int in_mode, int hv, int wv, int ho, int wo,
-                     void* ws, size_t ws_bytes, void* stream);
-/* Weight gradient of a 3x3 stride-1 pad-1 conv on the fp16 hi/lo split MFMA
- * (in_mode RAW / RELU / UPSAMPLE2, hv x wv = dy's spatial size with wv % 16 == 0,
- * cin and cout >= 16); x_amax / dy_amax are amax groups of x and dy.  Split-K
- * partials in ws (stx_conv2d_wgrad16_ws, 0 = unsupported shape), fixed-order sum. */
-size_t stx_conv2d_wgrad16_ws(int n, int cin, int cout, int in_mode, int hv, int wv);
-int stx_conv2d_wgrad16(const float* x, const float* dy, float* dw, int accumulate, int n,
-                       int cin, int h, int w, int cout, int in_mode, int hv, int wv,
-                       const float* x_amax, const float* dy_amax, void* ws, size_t ws_bytes,
-                       void* stream);
-/* Weight gradient of the 3x3 stride-2 pad-1 downsampling convs of ImageTransformNet
- * (stransfer/network.py:528-533; replaces the autograd conv2d weight gradient of
- * static_train :690-765) on the fp16 hi/lo split MFMA: raw input x [n][cin][h][w]
- * with h = 2 ho, w = 2 wo, dy [n][cout][ho][wo], wo % 16 == 0, cin / cout >= 16.
- * Workspace: stx_conv2d_wgrad16_s2_ws (0 = unsupported shape). */
-size_t stx_conv2d_wgrad16_s2_ws(int n, int cin, int cout, int ho, int wo);
-int stx_conv2d_wgrad16_s2(const float* x, const float* dy, float* dw, int accumulate, int n,
-                          int cin, int h, int w, int cout, int ho, int wo, const float* x_amax,
-                          const float* dy_amax, void* ws, size_t ws_bytes, void* stream);
-
-/* dW of the ImageTransformNet 9x9 stride-1 pad-4 layers whose one side has 1..3
- * channels and the other 32 (conv0 3->32, conv22 32->3; stransfer/network.py:525-527,
- * 605-609, trained by static_train :690-765) on the fp16 hi/lo split MFMA: the
- * 3-channel tensor is expanded per tap row in LDS, the 32-channel one streamed.
- * x_amax / dy_amax: amax groups (>= max|x|, max|dy|).  ws: per-block partials
- * (stx_conv2d_wgrad_few16_ws, 0 = unsupported shape), summed in a fixed order. */
-size_t stx_conv2d_wgrad_few16_ws(int n, int cin, int cout, int ks, int h, int w);
-int stx_conv2d_wgrad_few16(const float* x, const float* dy, float* dw, int accumulate, int n,
-                           int cin, int h, int w, int cout, int ks, int pad, const float* x_amax,
-                           const float* dy_amax, void* ws, size_t ws_bytes, void* stream);
+ * Split-K partial slabs in ws (fp32), reduced in fixed order (deterministic).  The caller
+ * describes the conv; the library picks the path from the dims alone: the first of FEW16,
+ * F16, F16S2 that covers them, else F32. */
+#define STX_WGRAD_NONE 0 /* unsupported: not ks 3 stride 1/2 or ks 9 stride 1, STX_IN_DILATE2,
+                          * or ho / wo that do not follow from the dims */
+/* Implicit GEMM on fp32 MFMA (wgrad.hip): every supported shape the paths below leave. */
+#define STX_WGRAD_F32 1
+/* 3x3 stride-1 pad-1 conv on the fp16 hi/lo split MFMA (wgrad16.hip; in_mode RAW / RELU /
+ * UPSAMPLE2, wo % 16 == 0, cin and cout >= 16); the upsampled input runs in the parity
+ * classes of stx_conv_weight_prep16_up. */
+#define STX_WGRAD_F16 2
+/* The 3x3 stride-2 pad-1 downsampling convs of ImageTransformNet (stransfer/network.py:
+ * 528-533; replaces the autograd conv2d weight gradient of static_train :690-765) on the
+ * split MFMA: raw input with h = 2 ho, w = 2 wo, wo % 16 == 0, cin / cout >= 16. */
+#define STX_WGRAD_F16S2 3
+/* dW of the ImageTransformNet 9x9 stride-1 pad-4 layers whose one side has 1..3 channels
+ * and the other 32 (conv0 3->32, conv22 32->3; stransfer/network.py:525-527, 605-609) on
+ * the split MFMA, raw input, w % 16 == 0 (wgrad9.hip): the 3-channel tensor is expanded
+ * per tap row in LDS, the 32-channel one streamed. */
+#define STX_WGRAD_FEW16 4
+typedef struct stx_wgrad_params {
+  const float* x;  /* [n][cin][h][w] */
+  const float* dy; /* [n][cout][ho][wo] */
+  float* dw;
+  /* amax groups (>= max|x|, max|dy|); required iff the planned path is a split one (> F32),
+   * which also needs x and dy 16-byte aligned */
+  const float* x_amax;
+  const float* dy_amax;
+  void* ws; /* at least the planner's ws_bytes */
+  size_t ws_bytes;
+  int accumulate;
+  int n, cin, h, w, cout, ks, stride, pad, in_mode, ho, wo;
+  int no_split; /* 1: STX_WGRAD_F32 whatever the shape (the tests' fp32 comparison) */
+} stx_wgrad_params;
+/* The path (STX_WGRAD_*) stx_conv2d_wgrad takes for p and its workspace bytes (ws_bytes may
+ * be NULL).  Reads only the dims, in_mode and no_split; needs no GPU. */
+int stx_conv2d_wgrad_plan(const stx_wgrad_params* p, size_t* ws_bytes);
+int stx_conv2d_wgrad(const stx_wgrad_params* p, void* stream);
 /* db[c] (+)= sum_{n,p} dy[n][c][p]  (conv bias gradient) */
 size_t stx_bias_grad_ws(int n, int c);
 int stx_bias_grad(const float* dy, float* db, int n, int c, int hw, int accumulate,

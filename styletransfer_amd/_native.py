@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("STX_LIB", os.path.join(_HERE, "libstx.so"))
 STX_IN_RAW, STX_IN_RELU, STX_IN_RELU_POOL2, STX_IN_UPSAMPLE2, STX_IN_DILATE2 = range(5)
 STX_AMAX_SLOTS = 32  # an "amax" is a group of 32 floats whose max is the value (stx.h)
 STX_GRAM_GROUP = 8  # fused Gram partials per in-kernel group sum (stx_conv_params.gram_cnt)
-STX_ABI_VERSION = 10 # include/stx.h: the library must report the same revision
+STX_ABI_VERSION = 11 # include/stx.h: the library must report the same revision
 
 
 def knob(name: str, default: str) -> str:
@@ -110,6 +110,15 @@ class StyleLossParams(C.Structure):
                 ("defer", C.POINTER(GramFinJob))]
 
 
+class WgradParams(C.Structure):
+    """Mirror of `stx_wgrad_params` (include/stx.h)."""
+    _fields_ = [("x", vp), ("dy", vp), ("dw", vp), ("x_amax", vp), ("dy_amax", vp), ("ws", vp),
+                ("ws_bytes", sz), ("accumulate", i32), ("n", i32), ("cin", i32), ("h", i32),
+                ("w", i32), ("cout", i32), ("ks", i32), ("stride", i32), ("pad", i32),
+                ("in_mode", i32), ("ho", i32), ("wo", i32), ("no_split", i32)]
+
+
+STX_WGRAD_NONE, STX_WGRAD_F32, STX_WGRAD_F16, STX_WGRAD_F16S2, STX_WGRAD_FEW16 = range(5)
 STX_FIN_MAX = 8
 STX_GUIDE_MAX = 4  # regions of a guided Gram (include/stx.h)
 
@@ -133,18 +142,8 @@ SIGNATURES = {
     "stx_conv_weight_compose16": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
     "stx_amax": (i32, [vp, i64, vp, vp]),
     "stx_conv_weight_prep_batch": (i32, [C.POINTER(WprepJob), i32, vp]),
-    "stx_conv2d_wgrad_ws": (sz, [i32, i32, i32, i32, i32, i32, i32]),
-    "stx_conv2d_wgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
-                               i32, i32, i32, i32, vp, sz, vp]),
-    "stx_conv2d_wgrad16_ws": (sz, [i32, i32, i32, i32, i32, i32]),
-    "stx_conv2d_wgrad16": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp,
-                                 vp, sz, vp]),
-    "stx_conv2d_wgrad16_s2_ws": (sz, [i32, i32, i32, i32, i32]),
-    "stx_conv2d_wgrad16_s2": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp,
-                                    vp, sz, vp]),
-    "stx_conv2d_wgrad_few16_ws": (sz, [i32, i32, i32, i32, i32, i32]),
-    "stx_conv2d_wgrad_few16": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp,
-                                     vp, sz, vp]),
+    "stx_conv2d_wgrad_plan": (i32, [C.POINTER(WgradParams), C.POINTER(sz)]),
+    "stx_conv2d_wgrad": (i32, [C.POINTER(WgradParams), vp]),
     "stx_vec_ws": (sz, []),
     "stx_vec_reduce": (i32, [vp, vp, i64, i32, vp, vp, vp, f32, vp, sz, vp]),
     "stx_vec_axpby": (i32, [vp, vp, i64, f32, vp, f32, f32, vp]),

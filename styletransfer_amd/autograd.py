@@ -89,8 +89,9 @@ class Conv2dFn(torch.autograd.Function):
                 x_amax = ops.amax(x)
         elif wt is None:
             wt = ops.conv_weight_prep(w.detach().contiguous())
-            if stride == 2 and _split_on() and w.requires_grad:
-                x_amax = ops.ARENA.lookup(x)  # for the split stride-2 wgrad (None: computed there)
+            if w.requires_grad and ops.wgrad_path(*x.shape, cout, ks, stride, pad, in_mode) \
+                    > N.STX_WGRAD_F32:
+                x_amax = ops.ARENA.lookup(x)  # for the split wgrad (None: computed there)
         if ks == 9 and cout <= 3 and cin <= 32:
             # conv22 (32 -> 3): the split 9x9 kernel takes a max|x| bound -- the producing
             # InstanceNorm's amax group inside the trainers (ops.ARENA), else computed here
@@ -121,8 +122,8 @@ class Conv2dFn(torch.autograd.Function):
         # max|dy| once for the split dgrad and the split wgrad
         dy_amax = None
         split_d = stride == 1 and _split_on() and pad == 1 and ops.split_eligible(cout, cin, ks, 1)
-        if (split_d and ctx.needs_input_grad[0]) or (ctx.needs_input_grad[1] and _split_on() and (
-                (ks == 3 and stride in (1, 2) and pad == 1) or ks == 9)):
+        if (split_d and ctx.needs_input_grad[0]) or (ctx.needs_input_grad[1] and ops.wgrad_path(
+                *x.shape, cout, ks, stride, pad, in_mode) > N.STX_WGRAD_F32):
             dy_amax = ops.ARENA.lookup(dy)
             if dy_amax is None:
                 dy_amax = ops.amax(dy)

@@ -45,7 +45,8 @@ extern "C" int stx_abi_layout(long long* out, int n) {
       (long long)sizeof(stx_image_meta),   (long long)offsetof(stx_image_meta, tmp_offset),
       (long long)sizeof(stx_cin_job),      (long long)offsetof(stx_cin_job, accumulate),
       (long long)sizeof(stx_style_loss_params),
-      (long long)offsetof(stx_style_loss_params, defer)};
+      (long long)offsetof(stx_style_loss_params, defer),
+      (long long)sizeof(stx_wgrad_params), (long long)offsetof(stx_wgrad_params, no_split)};
   const int m = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; out && i < n && i < m; ++i) out[i] = v[i];
   return m;

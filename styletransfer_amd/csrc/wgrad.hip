@@ -253,47 +253,88 @@ static bool wg_plan(int n, int cin, int cout, int ks, int stride, int ho, int wo
 }
 
 template <int KS, int S, int CIS, int WM, int WN, int NI, int NPIX, int TW>
-static void wg_launch(const WgPlan& pl, const float* x, const float* dy, float* ws, int n, int cin,
-                      int h, int w, int cout, int pad, int mode, int hv, int wv, int ho, int wo,
+static void wg_launch(const WgPlan& pl, const stx_wgrad_params& p, int hv, int wv,
                       hipStream_t st) {
   hipLaunchKernelGGL((wgrad_kernel<KS, S, CIS, WM, WN, NI, NPIX, TW>),
-                     dim3(pl.nsplit, pl.ncob, pl.ncc), dim3(64 * WM * WN), 0, st, x, dy, ws, n,
-                     cin, h, w, cout, pad, mode, hv, wv, ho, wo, pl.tiles_x, pl.tiles_per_img,
-                     pl.nsplit);
+                     dim3(pl.nsplit, pl.ncob, pl.ncc), dim3(64 * WM * WN), 0, st, p.x, p.dy,
+                     (float*)p.ws, p.n, p.cin, p.h, p.w, p.cout, p.pad, p.in_mode, hv, wv, p.ho,
+                     p.wo, pl.tiles_x, pl.tiles_per_img, pl.nsplit);
 }
+
+// the virtual input dims of p's loader; false: no weight gradient for these dims at all
+static bool wg_dims(const stx_wgrad_params& p, int& hv, int& wv) {
+  if (p.in_mode < STX_IN_RAW || p.in_mode > STX_IN_UPSAMPLE2 || p.n <= 0 || p.cin <= 0 ||
+      p.cout <= 0 || p.h <= 0 || p.w <= 0 || p.pad < 0 || p.ho <= 0 || p.wo <= 0 ||
+      !((p.ks == 3 && (p.stride == 1 || p.stride == 2)) || (p.ks == 9 && p.stride == 1)))
+    return false;
+  const int up = p.in_mode == STX_IN_UPSAMPLE2, pool = p.in_mode == STX_IN_RELU_POOL2;
+  hv = up ? 2 * p.h : (pool ? p.h / 2 : p.h);
+  wv = up ? 2 * p.w : (pool ? p.w / 2 : p.w);
+  return (hv + 2 * p.pad - p.ks) / p.stride + 1 == p.ho &&
+         (wv + 2 * p.pad - p.ks) / p.stride + 1 == p.wo;
+}
+
+// the split paths: workspace bytes for p's dims (0: not covered) and the launch of a
+// validated p
+size_t wgrad_few16_plan(const stx_wgrad_params& p);           // wgrad9.hip
+int wgrad_few16(const stx_wgrad_params& p, hipStream_t st);   // wgrad9.hip
+size_t wgrad_f16_plan(const stx_wgrad_params& p);             // wgrad16.hip
+int wgrad_f16(const stx_wgrad_params& p, hipStream_t st);     // wgrad16.hip
 
 }  // namespace stx
 
 using namespace stx;
 
-extern "C" size_t stx_conv2d_wgrad_ws(int n, int cin, int cout, int ks, int stride, int ho,
-                                      int wo) {
+extern "C" int stx_conv2d_wgrad_plan(const stx_wgrad_params* pp, size_t* ws_bytes) {
+  int hv, wv, path = STX_WGRAD_NONE;
+  size_t need = 0;
   WgPlan pl;
-  if (!wg_plan(n, cin, cout, ks, stride, ho, wo, pl)) return 0;
-  return (size_t)pl.nsplit * pl.ncob * pl.ncc * pl.bm * pl.bn * sizeof(float) + 256;
+  if (pp && wg_dims(*pp, hv, wv)) {
+    const stx_wgrad_params& p = *pp;
+    if (!p.no_split && (need = wgrad_few16_plan(p))) {
+      path = STX_WGRAD_FEW16;
+    } else if (!p.no_split && (need = wgrad_f16_plan(p))) {
+      path = p.stride == 2 ? STX_WGRAD_F16S2 : STX_WGRAD_F16;
+    } else if (wg_plan(p.n, p.cin, p.cout, p.ks, p.stride, p.ho, p.wo, pl)) {
+      path = STX_WGRAD_F32;
+      need = (size_t)pl.nsplit * pl.ncob * pl.ncc * pl.bm * pl.bn * sizeof(float) + 256;
+    }
+  }
+  if (ws_bytes) *ws_bytes = need;
+  return path;
 }
 
-extern "C" int stx_conv2d_wgrad(const float* x, const float* dy, float* dw, int accumulate,
-                                int n, int cin, int h, int w, int cout, int ks, int stride,
-                                int pad, int in_mode, int hv, int wv, int ho, int wo, void* ws,
-                                size_t ws_bytes, void* stream) {
-  WgPlan pl;
-  if (!wg_plan(n, cin, cout, ks, stride, ho, wo, pl) || n <= 0 || !x || !dy || !dw) {
-    set_error("stx_conv2d_wgrad: unsupported ks=%d stride=%d", ks, stride);
+extern "C" int stx_conv2d_wgrad(const stx_wgrad_params* pp, void* stream) {
+  size_t need = 0;
+  const int path = stx_conv2d_wgrad_plan(pp, &need);
+  if (path == STX_WGRAD_NONE) {
+    set_error("stx_conv2d_wgrad: null params, unsupported ks / stride / in_mode, or ho / wo "
+              "that do not follow from the dims");
     return STX_E_INVALID;
   }
-  if ((hv + 2 * pad - ks) / stride + 1 != ho || (wv + 2 * pad - ks) / stride + 1 != wo) {
-    set_error("stx_conv2d_wgrad: inconsistent output dims");
+  const stx_wgrad_params& p = *pp;
+  const bool split = path != STX_WGRAD_F32;
+  if (!p.x || !p.dy || !p.dw || (split && (!p.x_amax || !p.dy_amax))) {
+    set_error("stx_conv2d_wgrad: NULL x / dy / dw%s", split ? " / x_amax / dy_amax" : "");
     return STX_E_INVALID;
   }
-  const size_t need = stx_conv2d_wgrad_ws(n, cin, cout, ks, stride, ho, wo);
-  if (!ws || ws_bytes < need) {
-    set_error("stx_conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
+  if (!p.ws || p.ws_bytes < need) {
+    set_error("stx_conv2d_wgrad: workspace %zu < %zu", p.ws_bytes, need);
     return STX_E_WORKSPACE;
   }
+  if (split && ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.dy)) & 15)) {
+    set_error("stx_conv2d_wgrad: the split paths need 16-byte aligned x and dy");
+    return STX_E_INVALID;
+  }
   hipStream_t st = (hipStream_t)stream;
-  float* slabs = (float*)ws;
-#define WG_ARGS pl, x, dy, slabs, n, cin, h, w, cout, pad, in_mode, hv, wv, ho, wo, st
+  if (path == STX_WGRAD_FEW16) return wgrad_few16(p, st);
+  if (split) return wgrad_f16(p, st);
+  int hv, wv;
+  WgPlan pl;
+  wg_dims(p, hv, wv);
+  wg_plan(p.n, p.cin, p.cout, p.ks, p.stride, p.ho, p.wo, pl);
+  const int ks = p.ks, stride = p.stride;
+#define WG_ARGS pl, p, hv, wv, st
   if (ks == 3 && stride == 1) {
     if (pl.tw == 64) wg_launch<3, 1, 32, 2, 3, 3, 128, 64>(WG_ARGS);
     else if (pl.tw == 32) wg_launch<3, 1, 32, 2, 3, 3, 128, 32>(WG_ARGS);
@@ -307,10 +348,10 @@ extern "C" int stx_conv2d_wgrad(const float* x, const float* dy, float* dw, int 
     else wg_launch<9, 1, 3, 1, 4, 2, 128, 16>(WG_ARGS);
   }
 #undef WG_ARGS
-  const long long total = (long long)cout * cin * ks * ks;
+  const long long total = (long long)p.cout * p.cin * ks * ks;
   const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)slabs, dw,
-                     cout, cin, ks * ks, pl.bm, pl.bn, pl.cis, pl.ncob, pl.ncc, pl.nsplit,
-                     accumulate);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)p.ws,
+                     p.dw, p.cout, p.cin, ks * ks, pl.bm, pl.bn, pl.cis, pl.ncob, pl.ncc,
+                     pl.nsplit, p.accumulate);
   return check_launch("stx_conv2d_wgrad");
 }

@@ -1029,71 +1029,46 @@ static bool wg16_plan(int n, int cin, int cout, int in_mode, int hv, int wv, Wg1
   return true;
 }
 
-}  // namespace stx
+// p's conv on this path: stride 1 with p's loader, or the stride-2 downsampling form
+static bool wg16_plan(const stx_wgrad_params& p, Wg16& g) {
+  static const bool s2_on = STX_KNOB("STX_WG16_S2", 1) != 0;
+  if (p.ks != 3 || p.pad != 1) return false;
+  if (p.stride == 1) return wg16_plan(p.n, p.cin, p.cout, p.in_mode, p.ho, p.wo, g);
+  return p.stride == 2 && s2_on && p.in_mode == STX_IN_RAW && p.h == 2 * p.ho &&
+         p.w == 2 * p.wo && wg16_plan(p.n, p.cin, p.cout, WG16_S2, p.ho, p.wo, g);
+}
 
-using namespace stx;
-
-extern "C" size_t stx_conv2d_wgrad16_ws(int n, int cin, int cout, int in_mode, int hv, int wv) {
+// STX_WGRAD_F16 / F16S2 for stx_conv2d_wgrad (wgrad.hip): workspace bytes (0: not covered)
+size_t wgrad_f16_plan(const stx_wgrad_params& p) {
   Wg16 g;
-  if (!wg16_plan(n, cin, cout, in_mode, hv, wv, g)) return 0;
+  if (!wg16_plan(p, g)) return 0;
   return (size_t)g.nsplit * (g.mode == WG16_UPP ? 12 : 9) * g.cout32 * g.cin32 * sizeof(float);
 }
 
-extern "C" int stx_conv2d_wgrad16(const float* x, const float* dy, float* dw, int accumulate,
-                                  int n, int cin, int h, int w, int cout, int in_mode, int hv,
-                                  int wv, const float* x_amax, const float* dy_amax, void* ws,
-                                  size_t ws_bytes, void* stream) {
+int wgrad_f16(const stx_wgrad_params& p, hipStream_t st) {  // p validated by the caller
   Wg16 g;
-  if (!x || !dy || !dw || !x_amax || !dy_amax || !wg16_plan(n, cin, cout, in_mode, hv, wv, g)) {
-    set_error("stx_conv2d_wgrad16: unsupported shape/mode or NULL argument");
-    return STX_E_INVALID;
-  }
-  g.h = h;
-  g.w = w;
-  if ((in_mode == STX_IN_UPSAMPLE2 && (hv != 2 * h || wv != 2 * w)) ||
-      (in_mode == WG16_S2 && (h != 2 * hv || w != 2 * wv)) ||
-      (in_mode != STX_IN_UPSAMPLE2 && in_mode != WG16_S2 && (hv != h || wv != w))) {
-    set_error("stx_conv2d_wgrad16: virtual dims do not match the input mode");
-    return STX_E_INVALID;
-  }
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) {
-    set_error("stx_conv2d_wgrad16: 16-byte aligned tensors required");
-    return STX_E_INVALID;
-  }
-  const size_t need = stx_conv2d_wgrad16_ws(n, cin, cout, in_mode, hv, wv);
-  if (!ws || ws_bytes < need) {
-    set_error("stx_conv2d_wgrad16: workspace %zu < %zu", ws_bytes, need);
-    return STX_E_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
+  wg16_plan(p, g);
+  g.h = p.h;
+  g.w = p.w;
   const int units = g.nsplit * (g.mode == WG16_UPP ? 4 : 3) * g.ncot * g.ncit;
   const int blocks = g.lds ? g.nsplit * 3 * g.ncit : cdiv(units, 4);
-  hipLaunchKernelGGL(wg16_kernel(g), dim3(blocks), dim3(wg16_threads(g)), 0, st, x, dy,
-                     (float*)ws, x_amax, dy_amax, g);
-  const long long total = (long long)cout * cin * 9;
+  float* ws = (float*)p.ws;
+  hipLaunchKernelGGL(wg16_kernel(g), dim3(blocks), dim3(wg16_threads(g)), 0, st, p.x, p.dy, ws,
+                     p.x_amax, p.dy_amax, g);
+  const long long total = (long long)p.cout * p.cin * 9;
   if (g.mode == WG16_UPP) {
     hipLaunchKernelGGL(wgrad16up_reduce_kernel, dim3((int)((total + 63) / 64)), dim3(256), 0, st,
-                       (const float*)ws, dw, g, accumulate);
-    return check_launch("stx_conv2d_wgrad16 (parity classes)");
+                       (const float*)ws, p.dw, g, p.accumulate);
+    return check_launch("stx_conv2d_wgrad (split 3x3, parity classes)");
   }
   const int rblocks = (int)std::min<long long>((total + 255) / 256, 4096);
   if (rblocks < 512 && g.nsplit >= 32)
     hipLaunchKernelGGL(wgrad16_reduce4_kernel, dim3((int)((total + 63) / 64)), dim3(256), 0, st,
-                       (const float*)ws, dw, g, accumulate);
+                       (const float*)ws, p.dw, g, p.accumulate);
   else
     hipLaunchKernelGGL(wgrad16_reduce_kernel, dim3(rblocks), dim3(256), 0, st, (const float*)ws,
-                       dw, g, accumulate);
-  return check_launch("stx_conv2d_wgrad16");
+                       p.dw, g, p.accumulate);
+  return check_launch("stx_conv2d_wgrad (split 3x3)");
 }
 
-extern "C" size_t stx_conv2d_wgrad16_s2_ws(int n, int cin, int cout, int ho, int wo) {
-  return stx_conv2d_wgrad16_ws(n, cin, cout, WG16_S2, ho, wo);
-}
-
-extern "C" int stx_conv2d_wgrad16_s2(const float* x, const float* dy, float* dw, int accumulate,
-                                     int n, int cin, int h, int w, int cout, int ho, int wo,
-                                     const float* x_amax, const float* dy_amax, void* ws,
-                                     size_t ws_bytes, void* stream) {
-  return stx_conv2d_wgrad16(x, dy, dw, accumulate, n, cin, h, w, cout, WG16_S2, ho, wo, x_amax,
-                            dy_amax, ws, ws_bytes, stream);
-}
+}  // namespace stx

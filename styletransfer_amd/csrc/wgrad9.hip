@@ -247,52 +247,41 @@ bool w9_plan(int n, int cin, int cout, int ks, int h, int w, int& ns, int& s_is_
   return true;
 }
 
+bool w9_plan(const stx_wgrad_params& q, int& ns, int& s_is_x, int& units, int& tiles_x,
+             int& blocks) {
+  return q.stride == 1 && q.pad == 4 && q.in_mode == STX_IN_RAW && q.ho == q.h && q.wo == q.w &&
+         w9_plan(q.n, q.cin, q.cout, q.ks, q.h, q.w, ns, s_is_x, units, tiles_x, blocks);
+}
+
 }  // namespace
-}  // namespace stx
 
-using namespace stx;
-
-extern "C" size_t stx_conv2d_wgrad_few16_ws(int n, int cin, int cout, int ks, int h, int w) {
+// STX_WGRAD_FEW16 for stx_conv2d_wgrad (wgrad.hip): workspace bytes (0: not covered)
+size_t wgrad_few16_plan(const stx_wgrad_params& q) {
   int ns, sx, units, tiles_x, blocks;
-  if (!w9_plan(n, cin, cout, ks, h, w, ns, sx, units, tiles_x, blocks)) return 0;
+  if (!w9_plan(q, ns, sx, units, tiles_x, blocks)) return 0;
   return (size_t)blocks * W9_PART * sizeof(float);
 }
 
-extern "C" int stx_conv2d_wgrad_few16(const float* x, const float* dy, float* dw, int accumulate,
-                                      int n, int cin, int h, int w, int cout, int ks, int pad,
-                                      const float* x_amax, const float* dy_amax, void* ws,
-                                      size_t ws_bytes, void* stream) {
+int wgrad_few16(const stx_wgrad_params& q, hipStream_t st) {  // q validated by the caller
   int ns, sx, units, tiles_x, blocks;
-  if (!x || !dy || !dw || !x_amax || !dy_amax || pad != ks / 2 ||
-      !w9_plan(n, cin, cout, ks, h, w, ns, sx, units, tiles_x, blocks)) {
-    set_error("stx_conv2d_wgrad_few16: unsupported shape (9x9 pad 4, 1..3 <-> 32 channels, "
-              "w %% 16 == 0) or missing pointers");
-    return STX_E_INVALID;
-  }
-  if (!ws || ws_bytes < (size_t)blocks * W9_PART * sizeof(float)) {
-    set_error("stx_conv2d_wgrad_few16: workspace");
-    return STX_E_WORKSPACE;
-  }
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) {
-    set_error("stx_conv2d_wgrad_few16: 16-byte aligned x and dy required");
-    return STX_E_INVALID;
-  }
+  w9_plan(q, ns, sx, units, tiles_x, blocks);
   Wf9 p;
-  p.S = sx ? x : dy;
-  p.L = sx ? dy : x;
-  p.s_amax = sx ? x_amax : dy_amax;
-  p.l_amax = sx ? dy_amax : x_amax;
-  p.part = reinterpret_cast<float*>(ws);
-  p.n = n;
+  p.S = sx ? q.x : q.dy;
+  p.L = sx ? q.dy : q.x;
+  p.s_amax = sx ? q.x_amax : q.dy_amax;
+  p.l_amax = sx ? q.dy_amax : q.x_amax;
+  p.part = reinterpret_cast<float*>(q.ws);
+  p.n = q.n;
   p.ns = ns;
-  p.h = h;
-  p.w = w;
+  p.h = q.h;
+  p.w = q.w;
   p.sgn = sx ? 1 : -1;
   p.tiles_x = tiles_x;
   p.units = units;
-  hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(wgrad9_kernel, dim3(blocks), dim3(256), 0, st, p);
   hipLaunchKernelGGL(wgrad9_reduce_kernel, dim3(W9_PART / W9R_OB), dim3(W9R_OB * W9R_G), 0, st,
-                     p.part, blocks, dw, ns, sx, accumulate);
-  return check_launch("stx_conv2d_wgrad_few16");
+                     p.part, blocks, q.dw, ns, sx, q.accumulate);
+  return check_launch("stx_conv2d_wgrad (few-channel 9x9)");
 }
+
+}  // namespace stx

@@ -19,7 +19,7 @@ from ._native import ConvParams, check, lib
 
 __all__ = [
     "conv_weight_dims", "conv_weight_prep", "conv_weight_prep16", "split_eligible", "amax",
-    "conv2d", "conv_out_hw", "conv2d_wgrad",
+    "conv2d", "conv_out_hw", "conv2d_wgrad", "wgrad_path",
     "bias_grad", "gram", "style_loss", "gram_bwd", "guided_style_loss", "guided_gram_bwd", "mse", "diff_scale", "loss_combine",
     "maxpool2x2", "maxpool2x2_bwd", "relupool_bwd", "relu", "relu_bwd", "adam_step",
     "instnorm_fwd", "instnorm_bwd", "cin_mix", "upsample2x", "upsample2x_bwd", "tv_loss",
@@ -659,63 +659,46 @@ def conv_gram_groups(cin, cout, ho, wo, n=1, in_mode=N.STX_IN_RAW):
     return lib().stx_conv_gram_groups(C.byref(p))
 
 
+@functools.lru_cache(maxsize=None)
+def _wgrad_plan(n, cin, h, w, cout, ks, stride, pad, in_mode, ho, wo, no_split):
+    """(path, workspace bytes) of stx_conv2d_wgrad_plan; they depend on these dims alone."""
+    p = N.WgradParams(n=n, cin=cin, h=h, w=w, cout=cout, ks=ks, stride=stride, pad=pad,
+                      in_mode=in_mode, ho=ho, wo=wo, no_split=no_split)
+    need = C.c_size_t()
+    return lib().stx_conv2d_wgrad_plan(C.byref(p), C.byref(need)), need.value
+
+
+def wgrad_path(n, cin, h, w, cout, ks, stride=1, pad=None, in_mode=N.STX_IN_RAW, split=True):
+    """The N.STX_WGRAD_* path conv2d_wgrad takes for an x [n][cin][h][w]; above
+    N.STX_WGRAD_F32 it is a split one, which reads the amax groups of x and dy."""
+    pad = ks // 2 if pad is None else pad
+    ho, wo = conv_out_hw(*virtual_hw(h, w, in_mode, 0, 0), ks, stride, pad)
+    no_split = int(not (split and N.knob("STX_CONV_SPLIT", "1") != "0"))
+    return _wgrad_plan(n, cin, h, w, cout, ks, stride, pad, in_mode, ho, wo, no_split)[0]
+
+
 def conv2d_wgrad(x, dy, cin, cout, ks, stride=1, pad=None, in_mode=N.STX_IN_RAW, dw=None,
                  accumulate=False, split=True, x_amax=None, dy_amax=None):
-    """dW (+)= sum dy * V(x); 3x3 stride-1 / stride-2 shapes run on the fp16 hi/lo split
-    MFMA (stx_conv2d_wgrad16[_s2]) unless split=False or STX_CONV_SPLIT=0."""
+    """dW (+)= sum dy * V(x) (stx_conv2d_wgrad: the library picks the kernel -- wgrad_path);
+    split=False or STX_CONV_SPLIT=0 keeps every shape on the fp32 MFMA."""
     _req(x, "x")
     _req(dy, "dy")
     n, _, h, w = x.shape
     if pad is None:
         pad = ks // 2
-    hv, wv = virtual_hw(h, w, in_mode)
-    ho, wo = dy.shape[2], dy.shape[3]
     if dw is None:
         dw = torch.empty((cout, cin, ks, ks), device=x.device, dtype=torch.float32)
-    L = lib()
-    split = split and N.knob("STX_CONV_SPLIT", "1") != "0"
-    if split and ks == 9 and stride == 1 and pad == 4 and in_mode == N.STX_IN_RAW:
-        # ITN conv0 / conv22: the 3-channel side expanded per tap row (wgrad9.hip)
-        need9 = L.stx_conv2d_wgrad_few16_ws(n, cin, cout, ks, h, w)
-        if need9 and ho == h and wo == w:
-            xa = x_amax if x_amax is not None else amax(x)
-            da = dy_amax if dy_amax is not None else amax(dy)
-            wp, wn = _scratch().get(need9, x.device)
-            check(L.stx_conv2d_wgrad_few16(x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
-                                           int(accumulate), n, cin, h, w, cout, ks, pad,
-                                           xa.data_ptr(), da.data_ptr(), wp, wn, _stream()),
-                  "stx_conv2d_wgrad_few16")
-            return dw
-    if split and ks == 3 and stride == 1 and pad == 1:
-        need16 = L.stx_conv2d_wgrad16_ws(n, cin, cout, in_mode, ho, wo)
-        if need16:
-            _req(dy, "dy")
-            xa = x_amax if x_amax is not None else amax(x)
-            da = dy_amax if dy_amax is not None else amax(dy)
-            wp, wn = _scratch().get(need16, x.device)
-            check(L.stx_conv2d_wgrad16(x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
-                                       int(accumulate), n, cin, h, w, cout, in_mode, ho, wo,
-                                       xa.data_ptr(), da.data_ptr(), wp, wn, _stream()),
-                  "stx_conv2d_wgrad16")
-            return dw
-    if split and ks == 3 and stride == 2 and pad == 1 and in_mode == N.STX_IN_RAW \
-            and N.knob("STX_WG16_S2", "1") != "0" \
-            and h == 2 * ho and w == 2 * wo:
-        need16 = L.stx_conv2d_wgrad16_s2_ws(n, cin, cout, ho, wo)
-        if need16:
-            xa = x_amax if x_amax is not None else amax(x)
-            da = dy_amax if dy_amax is not None else amax(dy)
-            wp, wn = _scratch().get(need16, x.device)
-            check(L.stx_conv2d_wgrad16_s2(x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
-                                          int(accumulate), n, cin, h, w, cout, ho, wo,
-                                          xa.data_ptr(), da.data_ptr(), wp, wn, _stream()),
-                  "stx_conv2d_wgrad16_s2")
-            return dw
-    need = L.stx_conv2d_wgrad_ws(n, cin, cout, ks, stride, ho, wo)
-    wp, wn = _scratch().get(need, x.device)
-    check(L.stx_conv2d_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), int(accumulate), n, cin,
-                             h, w, cout, ks, stride, pad, in_mode, hv, wv, ho, wo, wp, wn,
-                             _stream()), "stx_conv2d_wgrad")
+    p = N.WgradParams(x=x.data_ptr(), dy=dy.data_ptr(), dw=dw.data_ptr(),
+                      accumulate=int(accumulate), n=n, cin=cin, h=h, w=w, cout=cout, ks=ks,
+                      stride=stride, pad=pad, in_mode=in_mode, ho=dy.shape[2], wo=dy.shape[3],
+                      no_split=int(not (split and N.knob("STX_CONV_SPLIT", "1") != "0")))
+    path, need = _wgrad_plan(n, cin, h, w, cout, ks, stride, pad, in_mode, p.ho, p.wo, p.no_split)
+    if path > N.STX_WGRAD_F32:  # (xa / da stay referenced until the launch is queued)
+        xa = x_amax if x_amax is not None else amax(x)
+        da = dy_amax if dy_amax is not None else amax(dy)
+        p.x_amax, p.dy_amax = xa.data_ptr(), da.data_ptr()
+    p.ws, p.ws_bytes = _scratch().get(need, x.device)
+    check(lib().stx_conv2d_wgrad(C.byref(p), _stream()), "stx_conv2d_wgrad")
     return dw
 
 

@@ -764,6 +764,7 @@ def test_split_wgrad(dev, case):
     y = F.conv2d(xv, wgt, padding=1)
     dy = rnd(*y.shape, dev=dev, seed=62, scale=2e-3, shift=-1e-3)
     (ref,) = torch.autograd.grad(y, wgt, dy.double().cpu())
+    assert ops.wgrad_path(n, cin, h, w, cout, 3, in_mode=mode) == N.STX_WGRAD_F16
     dw16 = ops.conv2d_wgrad(x, dy, cin, cout, 3, in_mode=mode)
     dw32 = ops.conv2d_wgrad(x, dy, cin, cout, 3, in_mode=mode, split=False)
     assert rel(dw16, ref) < TOL64, (rel(dw16, ref), rel(dw32, ref))
@@ -779,7 +780,7 @@ def test_split_wgrad_stride2(dev, case):
     x = rnd(n, cin, h, w, dev=dev, seed=64, scale=2, shift=-1)
     wgt = torch.zeros(cout, cin, 3, 3, dtype=torch.float64, requires_grad=True)
     y = F.conv2d(x.double().cpu(), wgt, stride=2, padding=1)
-    assert N.lib().stx_conv2d_wgrad16_s2_ws(n, cin, cout, y.shape[2], y.shape[3]) > 0
+    assert ops.wgrad_path(n, cin, h, w, cout, 3, stride=2) == N.STX_WGRAD_F16S2
     dy = rnd(*y.shape, dev=dev, seed=65, scale=2e-3, shift=-1e-3)
     (ref,) = torch.autograd.grad(y, wgt, dy.double().cpu())
     dw16 = ops.conv2d_wgrad(x, dy, cin, cout, 3, stride=2)
@@ -800,12 +801,33 @@ def test_split_wgrad_9x9_few(dev, case):
     y = F.conv2d(x.double().cpu(), wgt, padding=4)
     dy = rnd(*y.shape, dev=dev, seed=72, scale=2e-3, shift=-1e-3)
     (ref,) = torch.autograd.grad(y, wgt, dy.double().cpu())
+    assert ops.wgrad_path(n, cin, h, w, cout, 9) == N.STX_WGRAD_FEW16
     dw16 = ops.conv2d_wgrad(x, dy, cin, cout, 9)
     dw32 = ops.conv2d_wgrad(x, dy, cin, cout, 9, split=False)
     assert rel(dw16, ref) < TOL64, (rel(dw16, ref), rel(dw32, ref))
     acc = dw16.clone()
     ops.conv2d_wgrad(x, dy, cin, cout, 9, dw=acc, accumulate=True)
     assert rel(acc, 2 * ref) < TOL64
+
+
+@pytest.mark.parametrize("case", [((2, 32, 64, 32, 64), 3, 2, N.STX_WGRAD_F16S2),
+                                  ((2, 3, 32, 64, 64), 9, 1, N.STX_WGRAD_FEW16),
+                                  ((1, 128, 128, 3, 16), 3, 1, N.STX_WGRAD_F16),
+                                  ((1, 8, 8, 6, 16), 3, 1, N.STX_WGRAD_F32)])
+def test_wgrad_given_amax_bit_identical(dev, case):
+    """One case per path: dW with the amax groups handed in (the trainers' arena bound)
+    equals dW with them computed inside conv2d_wgrad, and a repeated call, bit for bit."""
+    (n, cin, cout, h, w), ks, stride, path = case
+    assert ops.wgrad_path(n, cin, h, w, cout, ks, stride=stride) == path
+    x = rnd(n, cin, h, w, dev=dev, seed=66, scale=2, shift=-1)
+    ho, wo = ops.conv_out_hw(h, w, ks, stride, ks // 2)
+    dy = rnd(n, cout, ho, wo, dev=dev, seed=67, scale=2e-3, shift=-1e-3)
+    own = ops.conv2d_wgrad(x, dy, cin, cout, ks, stride=stride)
+    given = ops.conv2d_wgrad(x, dy, cin, cout, ks, stride=stride, x_amax=ops.amax(x),
+                             dy_amax=ops.amax(dy))
+    again = ops.conv2d_wgrad(x, dy, cin, cout, ks, stride=stride)
+    assert torch.equal(own, given) and torch.equal(own, again)
+    assert float(own.abs().max()) > 0
 
 
 @pytest.mark.parametrize("shape", [(64, 64), (128, 32), (20, 70)])

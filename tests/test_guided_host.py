@@ -28,7 +28,7 @@ def test_guided_symbols_and_abi_revision():
         assert name in N.SIGNATURES, name
     hdr = open(os.path.join(REPO, "include", "stx.h")).read()
     rev = int(re.search(r"#define STX_ABI_VERSION (\d+)", hdr).group(1))
-    assert L.stx_abi_version() == 10 == rev == N.STX_ABI_VERSION
+    assert L.stx_abi_version() == 11 == rev == N.STX_ABI_VERSION
     assert int(re.search(r"#define STX_GUIDE_MAX (\d+)", hdr).group(1)) == 4 == N.STX_GUIDE_MAX
 
 

@@ -1,6 +1,7 @@
 """Host-side logic that needs no GPU: the C-ABI library loads and exports every
 declared symbol; image I/O parity with the reference; checkpoint helpers; module
 structure / state_dict keys; the product path fails loudly without a GPU."""
+import ctypes as C
 import os
 import re
 import subprocess
@@ -37,7 +38,8 @@ def test_struct_mirrors_match_the_library():
     from styletransfer_amd import _native as N
     mirrors = [(N.ConvParams, "unpool_out"), (N.WprepJob, "pad_"), (N.LossParts, "k"),
                (N.GramFinJob, "coef_amax"), (N.PGradJob, "pad_"), (N.ImageMeta, "tmp_offset"),
-               (N.CinJob, "accumulate"), (N.StyleLossParams, "defer")]
+               (N.CinJob, "accumulate"), (N.StyleLossParams, "defer"),
+               (N.WgradParams, "no_split")]
     count = N.lib().stx_abi_layout(None, 0)
     assert count == 2 * len(mirrors)
     out = (C.c_longlong * count)()
@@ -54,7 +56,94 @@ def test_host_queries_without_gpu():
     assert ops.coef_pitch(64) == 64 and ops.coef_pitch(96) == 128
     from styletransfer_amd import _native as N
     assert N.lib().stx_gram_ws(1, 64, 262144) > 0
-    assert N.lib().stx_conv2d_wgrad_ws(8, 128, 128, 3, 1, 64, 64) > 0
+    need = C.c_size_t()
+    p = N.WgradParams(n=8, cin=128, h=64, w=64, cout=128, ks=3, stride=1, pad=1, ho=64, wo=64)
+    assert N.lib().stx_conv2d_wgrad_plan(C.byref(p), C.byref(need)) > 0 and need.value > 0
+
+
+def _wgrad_dims(n, cin, h, w, cout, ks, stride=1, mode=0, **kw):
+    """stx_wgrad_params dims of a pad ks // 2 conv over x [n][cin][h][w] read with `mode`."""
+    from styletransfer_amd import _native as N
+    hv, wv = (2 * h, 2 * w) if mode == N.STX_IN_UPSAMPLE2 else (h, w)
+    pad = ks // 2
+    f = dict(n=n, cin=cin, h=h, w=w, cout=cout, ks=ks, stride=stride, pad=pad, in_mode=mode,
+             ho=(hv + 2 * pad - ks) // stride + 1, wo=(wv + 2 * pad - ks) // stride + 1)
+    f.update(kw)
+    return f
+
+
+def _wgrad_plan(**f):
+    from styletransfer_amd import _native as N
+    need = C.c_size_t()
+    return N.lib().stx_conv2d_wgrad_plan(C.byref(N.WgradParams(**f)), C.byref(need)), need.value
+
+
+def test_wgrad_path_table():
+    """The kernel stx_conv2d_wgrad picks is pinned per layer: every trained conv of
+    ImageTransformNet at B = 8, 256^2 and the VGG-style ReLU-input 3x3 convs take the path
+    the Python ladder over the per-kernel workspace probes gave them before the choice moved
+    into the library (run by hand on a build of that revision).  A plan function that sent
+    one of them to the fp32 kernel would pass every fp64 comparison and only be slower."""
+    from styletransfer_amd import _native as N
+    RELU, UP = N.STX_IN_RELU, N.STX_IN_UPSAMPLE2
+    table = [((8, 3, 256, 256, 32, 9), N.STX_WGRAD_FEW16),            # conv0
+             ((8, 32, 256, 256, 64, 3, 2), N.STX_WGRAD_F16S2),        # the two downs
+             ((8, 64, 128, 128, 128, 3, 2), N.STX_WGRAD_F16S2),
+             ((8, 128, 64, 64, 128, 3), N.STX_WGRAD_F16),             # residual blocks
+             ((8, 128, 64, 64, 64, 3, 1, UP), N.STX_WGRAD_F16),       # the two upsampled convs
+             ((8, 64, 128, 128, 32, 3, 1, UP), N.STX_WGRAD_F16),
+             ((8, 32, 256, 256, 3, 9), N.STX_WGRAD_FEW16),            # conv22
+             ((8, 64, 256, 256, 64, 3, 1, RELU), N.STX_WGRAD_F16),    # VGG-style
+             ((8, 64, 128, 128, 128, 3, 1, RELU), N.STX_WGRAD_F16)]
+    for args, want in table:
+        path, need = _wgrad_plan(**_wgrad_dims(*args))
+        assert path == want and need > 0, (args, path, need)
+        assert _wgrad_plan(**_wgrad_dims(*args, no_split=1))[0] == N.STX_WGRAD_F32, args
+    # shapes the split kernels do not cover fall through to the fp32 kernel
+    for args in ((2, 3, 32, 40, 32, 9),        # 9x9, w % 16 != 0
+                 (2, 32, 16, 24, 32, 3),       # 3x3 stride 1, wo % 16 != 0
+                 (2, 8, 16, 16, 32, 3),        # 3x3 stride 1, cin 8
+                 (2, 32, 17, 32, 32, 3, 2)):   # 3x3 stride 2, odd h
+        path, need = _wgrad_plan(**_wgrad_dims(*args))
+        assert path == N.STX_WGRAD_F32 and need > 0, (args, path, need)
+    # no kernel at all
+    for f in (_wgrad_dims(2, 32, 16, 16, 32, 5), _wgrad_dims(2, 32, 16, 16, 32, 3, 3),
+              _wgrad_dims(2, 32, 16, 16, 32, 3, 1, N.STX_IN_DILATE2)):
+        assert _wgrad_plan(**f) == (N.STX_WGRAD_NONE, 0), f
+
+
+def test_wgrad_malformed_params_rejected():
+    """stx_conv2d_wgrad validates the whole stx_wgrad_params before any launch (no GPU is
+    present here and the pointers are fake): invalid, or the workspace code."""
+    from styletransfer_amd import _native as N
+    L = N.lib()
+    dims = _wgrad_dims(8, 128, 64, 64, 128, 3)
+    path, need = _wgrad_plan(**dims)
+    assert path == N.STX_WGRAD_F16
+
+    def refused(code, **kw):
+        f = dict(dims, x=16, dy=32, dw=48, x_amax=64, dy_amax=192, ws=4096, ws_bytes=need)
+        f.update(kw)
+        rc = L.stx_conv2d_wgrad(C.byref(N.WgradParams(**f)), None)
+        msg = L.stx_last_error_string()
+        assert rc == code and b"stx_conv2d_wgrad" in msg, (kw, rc, msg)
+
+    rc = L.stx_conv2d_wgrad(C.byref(N.WgradParams()), None)  # all zero
+    assert rc == 1001 and b"stx_conv2d_wgrad" in L.stx_last_error_string()
+    refused(1001, dw=None)
+    refused(1001, x=None)
+    refused(1001, dy_amax=None)             # a split path reads both amax groups
+    refused(1001, x_amax=None)
+    refused(1002, ws_bytes=need - 1)
+    refused(1002, ws=None)
+    refused(1001, ho=63)                    # ho does not follow from (h, ks, stride, pad)
+    refused(1001, in_mode=N.STX_IN_UPSAMPLE2)  # (ho would be 128)
+    refused(1001, x=20)                     # misaligned x on a split path: no fallback
+    refused(1001, dy=36)
+    refused(1001, ks=5)
+    # the fp32 path needs neither amax groups nor alignment, but its own workspace
+    need32 = _wgrad_plan(**dict(dims, no_split=1))[1]
+    refused(1002, no_split=1, x=20, x_amax=None, dy_amax=None, ws_bytes=need32 - 1)
 
 
 def test_invalid_args_rejected():

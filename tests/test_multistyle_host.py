@@ -15,7 +15,7 @@ E_INVALID = 1001
 
 
 def test_cin_job_mirror_matches_the_library():
-    mirrors = 8  # stx_abi_layout's table (include/stx.h); stx_cin_job is its seventh entry
+    mirrors = 9  # stx_abi_layout's table (include/stx.h); stx_cin_job is its seventh entry
     count = N.lib().stx_abi_layout(None, 0)
     assert count == 2 * mirrors
     out = (C.c_longlong * count)()
