@@ -784,6 +784,72 @@ int stx_resample2d(const float* x, float* y, int nc, int hi, int wi, int ho, int
                    const int* yfirst, const int* ycount, const float* yw, int yk, void* ws,
                    size_t ws_bytes, void* stream);
 
+/* Dense optical flow between two conditioned frames (the input of the flow entry points
+ * above): coarse-to-fine Horn-Schunck with warping, relaxed by Jacobi iterations.  For
+ * frames A, B [n][3][h][w], h, w >= 2, the estimate f [n][2][h][w] (channel 0 = dx, 1 = dy,
+ * in pixels) satisfies A(i, j) ~ B(i + f[1], j + f[0]): the flow that maps frame t onto
+ * frame t-1 is the estimate of (frame t, frame t-1).  The method, which the entry points
+ * below compose (video.FlowEstimator does; every fp32 expression is evaluated as written,
+ * an fmaf where one is written and no other fusing):
+ *
+ * 1. Luma (stx_flow_luma), grey [n][h][w]: with R = fmaf(r, std[0], mean[0]), G, B likewise
+ *    (mean, std_: HOST arrays of 3, as stx_image_condition's),
+ *      g = 255 * fmaf(0.114, B, fmaf(0.587, G, 0.299 * R)).
+ *
+ * 2. Pyramid (stx_flow_pyramid, HOST function, needs no GPU): level 0 is (h, w); level l+1
+ *    is (ceil(h_l / 2), ceil(w_l / 2)), added while min(h_l, w_l) div 2 >= min_side
+ *    (min_side >= 2).  Fills hs[], ws[] (both or neither; min(levels, cap) entries) and
+ *    returns the level count, -STX_E_INVALID on a bad argument.  A level's luma planes are
+ *    the finer level's through stx_resample2d, STX_FILTER_TRIANGLE; the flow is zero on the
+ *    coarsest level.
+ *
+ * 3. Linearise at the flow (u, v) = (flow[0], flow[1]) (stx_flow_linearize), per pixel:
+ *      y = fminf(fmaxf(i + v, 0), h-1), x = fminf(fmaxf(j + u, 0), w-1)   (fp32)
+ *    so that no bit pattern of a flow indexes outside the plane: fmaxf returns 0 for a NaN
+ *    sum, which then samples row / column 0.  Taps and weights are stx_flow_warp's:
+ *    y0 = min(floor(y), h-2), fy = y - y0, likewise x; w00 = (1-fy)(1-fx), w01 = (1-fy) fx,
+ *    w10 = fy (1-fx), w11 = fy fx; a sampled plane P is
+ *      S(P) = fmaf(w11, P11, fmaf(w10, P10, fmaf(w01, P01, w00 * P00))).
+ *    With Bx[i][j] = 0.5 (B[i][min(j+1, w-1)] - B[i][max(j-1, 0)]) and By likewise along the
+ *    rows (formed from the 4 x 4 neighbourhood of B around the taps, never stored):
+ *      coef[0] = Ix = S(Bx), coef[1] = Iy = S(By),
+ *      coef[2] = c = fmaf(Iy, v, fmaf(Ix, u, A - S(B))).
+ *    coef is [n][3][h][w] and must not be flow.
+ *
+ * 4. Jacobi (stx_flow_jacobi): `iters` iterations from uv_in, both channels from the
+ *    previous iterate.  With a2 = alpha * alpha, N, S, W, E the edge and NW, NE, SW, SE the
+ *    corner neighbours of a plane, indices clamped to the plane (replicated edges):
+ *      ubar = fmaf((NW + NE) + (SW + SE), 1/12, ((N + S) + (W + E)) * (1/6))
+ *      ru   = 1 / fmaf(Ix, Ix, a2),  rv = 1 / fmaf(Iy, Iy, a2)      (IEEE division)
+ *      u'   = fmaf(fmaf(-Iy, v, c), Ix, a2 * ubar) * ru
+ *      v'   = fmaf(fmaf(-Ix, u, c), Iy, a2 * vbar) * rv
+ *    (1/6 and 1/12 rounded to fp32).  fuse iterations run in one launch: a block relaxes a
+ *    32 x 32 tile with a halo of STX_FLOW_JACOBI_MAXFUSE cells in LDS and writes the tile;
+ *    every cell is computed by the same instructions whatever the fusion, so the result
+ *    does not depend on fuse, bit for bit.  fuse = 0: the library's choice (MAXFUSE; all
+ *    of iters where one tile covers the image); 1 <= fuse <= MAXFUSE: exactly that many
+ *    per launch, the last launch the remainder.  With more than one launch the iterates
+ *    alternate between uv_out and ws (stx_flow_jacobi_ws bytes); uv_in is never written.
+ *    uv_out must not overlap uv_in, ws neither.  alpha > 0, iters >= 1.
+ *
+ * 5. Prolongation: both channels through stx_resample2d (triangle) to the finer level,
+ *    then stx_flow_scale, in place: flow[0] *= sx, flow[1] *= sy with sx = (float)w_fine /
+ *    (float)w_coarse, sy likewise in h.
+ *
+ * Per level, `warps` times: step 3 at the current flow, then step 4 from it.
+ * None of these allocates or synchronises; arguments are checked before any launch.
+ * n <= 65535, h w < 2^29. */
+#define STX_FLOW_JACOBI_MAXFUSE 8
+int stx_flow_pyramid(int h, int w, int min_side, int* hs, int* ws, int cap);
+int stx_flow_luma(const float* img, float* grey, int n, int h, int w, const float* mean,
+                  const float* std_, void* stream);
+int stx_flow_linearize(const float* a, const float* b, const float* flow, float* coef, int n,
+                       int h, int w, void* stream);
+size_t stx_flow_jacobi_ws(int n, int h, int w);
+int stx_flow_jacobi(const float* coef, const float* uv_in, float* uv_out, int n, int h, int w,
+                    float alpha, int iters, int fuse, void* ws, size_t ws_bytes, void* stream);
+int stx_flow_scale(float* flow, int n, int h, int w, float sx, float sy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("STX_LIB", os.path.join(_HERE, "libstx.so"))
 STX_IN_RAW, STX_IN_RELU, STX_IN_RELU_POOL2, STX_IN_UPSAMPLE2, STX_IN_DILATE2 = range(5)
 STX_AMAX_SLOTS = 32  # an "amax" is a group of 32 floats whose max is the value (stx.h)
 STX_GRAM_GROUP = 8  # fused Gram partials per in-kernel group sum (stx_conv_params.gram_cnt)
+STX_FLOW_JACOBI_MAXFUSE = 8  # the most Jacobi iterations one tiled launch fuses (stx.h)
 STX_ABI_VERSION = 11 # include/stx.h: the library must report the same revision
 
 
@@ -209,6 +210,12 @@ SIGNATURES = {
     "stx_flow_consistency": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "stx_masked_mse_ws": (sz, []),
     "stx_masked_mse": (i32, [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, i32, vp, sz, vp]),
+    "stx_flow_pyramid": (i32, [i32, i32, i32, vp, vp, i32]),
+    "stx_flow_luma": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+    "stx_flow_linearize": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "stx_flow_jacobi_ws": (sz, [i32, i32, i32]),
+    "stx_flow_jacobi": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, sz, vp]),
+    "stx_flow_scale": (i32, [vp, i32, i32, i32, f32, f32, vp]),
 }
 
 _lib = None

@@ -12,23 +12,27 @@ LOGGER = c_logging.get_logger()
 
 
 def parse_flow(ctx, param, value):
-    """--flow static | FLOWS.npz (an existing file under the project root)."""
-    if value == "static":
+    """--flow static | auto | FLOWS.npz (an existing file under the project root)."""
+    if value in ("static", "auto"):
         return value
     path = os.path.join(constants.PROJECT_ROOT_PATH, value)
     if not os.path.isfile(path):
-        raise click.BadParameter(f"'{value}': 'static' or an .npz file with 'forward' and "
-                                 "'backward' flows expected", param_hint="--flow")
+        raise click.BadParameter(f"'{value}': 'static', 'auto' or an .npz file with 'forward' "
+                                 "and 'backward' flows expected", param_hint="--flow")
     return path
 
 
 @click.command()
 @click.argument("frames-path")
 @click.argument("style-image-path")
-@click.option("--flow", required=True, callback=parse_flow, metavar="FLOWS.npz|static",
+@click.option("--flow", required=True, callback=parse_flow, metavar="FLOWS.npz|static|auto",
               help="Optical flows between the conditioned frames: an .npz with 'forward' and "
                    "'backward', each [T-1, 2, S, S] float32 in pixels at the working "
-                   "resolution (channel 0 = columns, 1 = rows); static = a fixed camera")
+                   "resolution (channel 0 = columns, 1 = rows); static = a fixed camera; "
+                   "auto = estimated on the GPU (coarse-to-fine Horn-Schunck)")
+@click.option("--save-flows", default=None, metavar="PATH.npz",
+              help="With --flow auto: also write the estimated flows to this .npz, which a "
+                   "later run takes as --flow")
 @click.option("-s", "--steps", default=100, type=click.IntRange(min=0),
               help="Iterations per frame after the first")
 @click.option("--first-steps", default=None, type=click.IntRange(min=0),
@@ -48,18 +52,25 @@ def parse_flow(ctx, param, value):
               help="Multipliers of the style weight per style tap, conv1_1 .. conv3_1")
 @click.option("-o", "--out-dir", default="results/gatys_video/",
               help="Where the stylised frames 0.png, 1.png, ... are written")
-def gatys_video(frames_path, style_image_path, flow, steps, first_steps, temporal_weight,
-                content_weight, style_weight, optimizer, layer_weights, out_dir):
+def gatys_video(frames_path, style_image_path, flow, save_flows, steps, first_steps,
+                temporal_weight, content_weight, style_weight, optimizer, layer_weights, out_dir):
     """Gatys style transfer of a clip, consistent from frame to frame.
     FRAMES_PATH: a directory of frames or a .npy array [T, H, W, 3] uint8."""
     from .. import img_utils, network, video
     root = constants.PROJECT_ROOT_PATH
+    if save_flows is not None and flow != "auto":
+        raise click.UsageError("--save-flows needs --flow auto (there is nothing estimated "
+                               "to save otherwise)")
     src = os.path.join(root, frames_path)
     frames = list(video.iterate_frames(src))
     if not frames:
         raise click.UsageError(f"no frames in {frames_path}")
     flows = flow
-    if flow != "static":
+    if save_flows is not None:
+        # estimated up front and handed on as explicit flows: the same bits as auto's
+        flows = video.estimate_flows(frames)
+        video.save_flows(os.path.join(root, save_flows), *flows)
+    elif flow not in ("static", "auto"):
         try:
             flows = video.load_flows(flow, len(frames), frames[0].shape[-1])
         except ValueError as e:

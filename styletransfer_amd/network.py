@@ -429,7 +429,8 @@ class StyleNetwork(nn.Module):
                           content_weight=1, style_layer_weights=None):
         """Temporally consistent Gatys transfer of a clip (video.gatys_video; Ruder et al.
         2016): an iterator of stylised frames.  frames: conditioned frames [1, 3, h, w];
-        flows: "static" or (forward, backward) at the frames' resolution."""
+        flows: "static", "auto" (estimated on the GPU, video.FlowEstimator) or (forward,
+        backward) at the frames' resolution."""
         from . import video
         tw = video.DEFAULT_TEMPORAL_WEIGHT if temporal_weight is None else temporal_weight
         return video.gatys_video(self.features(), frames, _dev(style_image), flows, steps,

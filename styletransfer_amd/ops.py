@@ -26,6 +26,7 @@ __all__ = [
     "temporal_loss", "temporal_loss_bwd", "flow_warp", "flow_consistency", "masked_mse",
     "color_stats", "color_affine", "resample_plan",
     "resample2d",
+    "flow_pyramid", "flow_luma", "flow_linearize", "flow_jacobi", "flow_scale",
 ]
 
 
@@ -1440,3 +1441,90 @@ def resample2d(x, size, filter="cubic", out=None):
                            _p(xw), xk, _p(yf), _p(yc), _p(yw), yk, wp, wn, _stream()),
           "stx_resample2d")
     return out
+
+
+# ----------------------------------------------------------------- optical-flow estimation
+def flow_pyramid(h, w, min_side=16):
+    """[(h_0, w_0), (h_1, w_1), ...]: the levels of the flow estimator's pyramid, finest
+    first (stx_flow_pyramid: a host function, no GPU needed)."""
+    L = lib()
+    n = L.stx_flow_pyramid(int(h), int(w), int(min_side), None, None, 0)
+    if n <= 0:
+        check(-n, "stx_flow_pyramid")
+    hs, ws = (C.c_int * n)(), (C.c_int * n)()
+    if L.stx_flow_pyramid(int(h), int(w), int(min_side), hs, ws, n) != n:
+        check(1001, "stx_flow_pyramid")  # (1001: STX_E_INVALID)
+    return list(zip(hs, ws))
+
+
+def flow_luma(img, mean=None, std=None, out=None):
+    """grey [n, h, w] = 255 (0.299 R + 0.587 G + 0.114 B) of a conditioned image
+    [n, 3, h, w], R = r std[0] + mean[0] and so on (stx_flow_luma; mean, std default to
+    ImageNet's, as image conditioning applies them)."""
+    from . import constants
+    _img3(img, "img")
+    n, _, h, w = img.shape
+    if out is None:
+        out = torch.empty((n, h, w), device=img.device, dtype=torch.float32)
+    _req(out, "out")
+    assert out.numel() == n * h * w, (out.shape, img.shape)
+    check(lib().stx_flow_luma(img.data_ptr(), out.data_ptr(), n, h, w,
+                              _host_f32(constants.IMAGENET_MEAN if mean is None else mean, 3, "mean"),
+                              _host_f32(constants.IMAGENET_STD if std is None else std, 3, "std"),
+                              _stream()), "stx_flow_luma")
+    return out
+
+
+def _grey(t, name, flow):
+    _req(t, name)
+    if t.dim() != 3 or (t.shape[0], *t.shape[1:]) != (flow.shape[0], *flow.shape[2:]):
+        raise N.NativeError(f"{name}: [n, h, w] of the flow {tuple(flow.shape)} required "
+                            f"(got {tuple(t.shape)})")
+    return t
+
+
+def flow_linearize(a, b, flow, out=None):
+    """coef [n, 3, h, w] = (Ix, Iy, c) of luma planes a, b [n, h, w] at the flow [n, 2, h, w]:
+    b and its central-difference gradient sampled at the clamped (i + flow[1], j + flow[0]),
+    c = a - b_warped + Ix u + Iy v (stx_flow_linearize)."""
+    _flow2(flow, "flow")
+    _grey(a, "a", flow)
+    _grey(b, "b", flow)
+    n, _, h, w = flow.shape
+    if out is None:
+        out = torch.empty((n, 3, h, w), device=flow.device, dtype=torch.float32)
+    _req(out, "out")
+    assert tuple(out.shape) == (n, 3, h, w), (out.shape, flow.shape)
+    check(lib().stx_flow_linearize(a.data_ptr(), b.data_ptr(), flow.data_ptr(), out.data_ptr(),
+                                   n, h, w, _stream()), "stx_flow_linearize")
+    return out
+
+
+def flow_jacobi(coef, uv, out=None, alpha=15.0, iters=40, fuse=0):
+    """`iters` Jacobi iterations of the Horn-Schunck system of coef [n, 3, h, w] from uv
+    [n, 2, h, w] (stx_flow_jacobi).  fuse: iterations per launch (0: the library's choice);
+    the result does not depend on it.  out must not alias uv."""
+    _flow2(uv, "uv")
+    _req(coef, "coef")
+    n, _, h, w = uv.shape
+    if tuple(coef.shape) != (n, 3, h, w):
+        raise N.NativeError(f"coef: {(n, 3, h, w)} required (got {tuple(coef.shape)})")
+    if out is None:
+        out = torch.empty_like(uv)
+    _flow2(out, "out", uv)
+    L = lib()
+    wp, wn = _scratch().get(L.stx_flow_jacobi_ws(n, h, w), uv.device)
+    check(L.stx_flow_jacobi(coef.data_ptr(), uv.data_ptr(), out.data_ptr(), n, h, w,
+                            float(alpha), int(iters), int(fuse), wp, wn, _stream()),
+          "stx_flow_jacobi")
+    return out
+
+
+def flow_scale(flow, sx, sy):
+    """flow[:, 0] *= sx, flow[:, 1] *= sy in place (stx_flow_scale: a prolonged flow's
+    displacements in the finer level's pixels)."""
+    _flow2(flow, "flow")
+    n, _, h, w = flow.shape
+    check(lib().stx_flow_scale(flow.data_ptr(), n, h, w, float(sx), float(sy), _stream()),
+          "stx_flow_scale")
+    return flow

@@ -256,13 +256,102 @@ def load_flows(path, n_frames, size):
     return out[0], out[1]
 
 
+def save_flows(path, forward, backward):
+    """Write the .npz that load_flows reads: float32 'forward' and 'backward', each
+    [T-1, 2, S, S]."""
+    f, b = (np.ascontiguousarray(a, dtype=np.float32) for a in (forward, backward))
+    if f.shape != b.shape or f.ndim != 4 or f.shape[1] != 2:
+        raise ValueError(f"flows [T-1, 2, h, w] of one shape expected (got {f.shape}, {b.shape})")
+    with open(path, "wb") as fh:  # (a file object: numpy appends no second .npz to the name)
+        np.savez(fh, forward=f, backward=b)
+
+
+class FlowEstimator:
+    """Dense optical flow between two conditioned frames on the GPU: coarse-to-fine
+    Horn-Schunck with warping, relaxed by Jacobi iterations (include/stx.h).
+
+    pair(prev, cur) -> (fwd, bwd), static [1, 2, h, w] tensors in this project's conventions
+    (channel 0 = dx, 1 = dy, in pixels; bwd maps cur onto prev): both directions run as one
+    batch of two.  Every level's buffers and the resample tables are made here; pair
+    allocates nothing, synchronises nothing and can be captured (ops.graph_capture).  The
+    estimator holds no graph: whoever captures pair owns the graph."""
+
+    def __init__(self, h, w, device=None, alpha=15.0, warps=5, iters=40, min_side=16,
+                 mean=None, std=None):
+        if warps < 1 or iters < 1:
+            raise ValueError(f"warps {warps}, iters {iters}: at least 1 each")
+        self.dev = torch.device(device or constants.DEVICE)
+        self.alpha, self.warps, self.iters = float(alpha), int(warps), int(iters)
+        self.mean, self.std = mean, std
+        self.levels = ops.flow_pyramid(h, w, min_side)
+        z = lambda *s: torch.zeros(s, device=self.dev, dtype=torch.float32)
+        # per level: luma [A | B] = [(prev, cur) | (cur, prev)], two flow buffers, coefficients
+        self.grey = [z(2, 2, hl, wl) for hl, wl in self.levels]
+        self.uv = [(z(2, 2, hl, wl), z(2, 2, hl, wl)) for hl, wl in self.levels]
+        self.coef = [z(2, 3, hl, wl) for hl, wl in self.levels]
+        # level 0 starts in the buffer from which `warps` swaps end in uv[0][0]
+        self.flow = self.uv[0][0]
+        self.fwd, self.bwd = self.flow[0:1], self.flow[1:2]
+        self.pair(z(1, 3, h, w), z(1, 3, h, w))  # uploads the tables, sizes the scratch
+        torch.cuda.synchronize(self.dev)
+
+    def pair(self, prev, cur):
+        g0 = self.grey[0]
+        for img, a_slot, b_slot in ((prev, 0, 1), (cur, 1, 0)):
+            ops.flow_luma(img, self.mean, self.std, out=g0[0, a_slot:a_slot + 1])
+            ops.flow_luma(img, self.mean, self.std, out=g0[1, b_slot:b_slot + 1])
+        for l in range(1, len(self.levels)):
+            ops.resample2d(self.grey[l - 1], self.levels[l], "triangle", out=self.grey[l])
+        top = len(self.levels) - 1
+        for l in range(top, -1, -1):
+            hl, wl = self.levels[l]
+            # `warps` swaps must end in buffer 0 (level 0: the static output)
+            src = self.warps % 2
+            if l == top:
+                self.uv[l][src].zero_()
+            else:
+                hc, wc = self.levels[l + 1]
+                ops.resample2d(self.uv[l + 1][0], (hl, wl), "triangle", out=self.uv[l][src])
+                ops.flow_scale(self.uv[l][src], np.float32(wl) / np.float32(wc),
+                               np.float32(hl) / np.float32(hc))
+            for _ in range(self.warps):
+                cur_uv, nxt = self.uv[l][src], self.uv[l][src ^ 1]
+                ops.flow_linearize(self.grey[l][0], self.grey[l][1], cur_uv, out=self.coef[l])
+                ops.flow_jacobi(self.coef[l], cur_uv, out=nxt, alpha=self.alpha, iters=self.iters)
+                src ^= 1
+        return self.fwd, self.bwd
+
+
+def estimate_flows(frames, device=None, **params):
+    """(forward, backward) of a clip's conditioned frames [1, 3, S, S]: float32 arrays
+    [T-1, 2, S, S], what load_flows returns (FlowEstimator; params: its keywords)."""
+    dev = torch.device(device or constants.DEVICE)
+    est, prev, fwd, bwd = None, None, [], []
+    for frame in frames:
+        frame = frame.to(dev, torch.float32).contiguous()
+        if est is None:
+            est = FlowEstimator(frame.shape[-2], frame.shape[-1], dev, **params)
+        if prev is not None:
+            f, b = est.pair(prev, frame)
+            fwd.append(f[0].cpu().numpy())
+            bwd.append(b[0].cpu().numpy())
+        prev = frame
+    if est is None:
+        raise ValueError("estimate_flows: no frames")
+    shape = (0, 2) + tuple(prev.shape[-2:])
+    return (np.stack(fwd) if fwd else np.zeros(shape, np.float32),
+            np.stack(bwd) if bwd else np.zeros(shape, np.float32))
+
+
 def gatys_video(feat, frames, style_image, flows, steps, first_steps=None,
                 temporal_weight=DEFAULT_TEMPORAL_WEIGHT, optimizer="adam", style_weight=100_000,
                 content_weight=1, style_layer_weights=None, lr=1e-3) -> Iterator[torch.Tensor]:
     """Stylised frames [1, 3, h, w] of a clip, one Gatys optimisation per frame (Ruder,
     Dosovitskiy & Brox 2016, short-term consistency).  frames: conditioned frames, as
-    iterate_frames yields them; flows: "static" (a fixed camera: zero flow both ways) or
-    (forward, backward), each [T-1, 2, h, w] (load_flows).  Frame 0 runs first_steps
+    iterate_frames yields them; flows: "static" (a fixed camera: zero flow both ways), "auto"
+    (FlowEstimator.pair(frame t-1, frame t) before each frame t >= 1: the flows that
+    estimate_flows returns, bit for bit) or (forward, backward), each [T-1, 2, h, w]
+    (load_flows).  Frame 0 runs first_steps
     (default steps) from the content frame.  Frame t >= 1 starts from the previous result
     warped along backward[t-1] (the frame itself where the warp leaves the image) and adds
 
@@ -275,9 +364,10 @@ def gatys_video(feat, frames, style_image, flows, steps, first_steps=None,
     if optimizer not in ("adam", "lbfgs"):
         raise ValueError(f"optimizer {optimizer!r}: 'adam' or 'lbfgs'")
     dev = feat.device
-    static = isinstance(flows, str)
-    if static and flows != "static":
-        raise ValueError(f"flows {flows!r}: 'static' or (forward, backward)")
+    if isinstance(flows, str) and flows not in ("static", "auto"):
+        raise ValueError(f"flows {flows!r}: 'static', 'auto' or (forward, backward)")
+    static, auto = flows == "static", flows == "auto"
+    est = last = None
     first_steps = steps if first_steps is None else first_steps
     targets = feat.style_targets(style_image.to(dev, torch.float32))
     kw = dict(style_weight=style_weight, content_weight=content_weight, targets=targets,
@@ -301,6 +391,12 @@ def gatys_video(feat, frames, style_image, flows, steps, first_steps=None,
         else:
             if static:
                 fwd = bwd = zero
+            elif auto:
+                # launched eagerly: the host is a frame's iterations ahead of the device, and
+                # a replayed capture of the estimator measured slower here
+                if est is None:
+                    est = FlowEstimator(h, w, dev)
+                fwd, bwd = est.pair(last, frame)
             else:
                 if t - 1 >= len(flows[0]):
                     raise ValueError(f"frame {t}: only {len(flows[0])} flows given")
@@ -321,4 +417,8 @@ def gatys_video(feat, frames, style_image, flows, steps, first_steps=None,
                                    temporal=(omega, cmask, temporal_weight), **kw)
                 eng.run(steps)
         prev.copy_(eng.x.detach())
+        if auto:
+            if last is None:
+                last = torch.empty_like(frame)
+            last.copy_(frame)
         yield prev.clone()
