@@ -194,8 +194,8 @@ const char* stx_last_error_string(void);
  * 9: the guided Gram entry points; 10: stx_style_loss takes stx_style_loss_params; 11:
  * stx_conv2d_wgrad takes stx_wgrad_params).  The revision moves only when an existing
  * entry point or struct changes meaning; entry points that are merely added (the colour
- * control pair, the flow entry points below) do not bump it -- a binding finds a missing
- * symbol at load. */
+ * control pair, the flow entry points below, stx_flow_compose) do not bump it -- a binding
+ * finds a missing symbol at load. */
 #define STX_ABI_VERSION 11
 int stx_abi_version(void);
 
@@ -718,7 +718,30 @@ int stx_temporal_loss_bwd(const float* y, const float* y_old, long long n, const
  * take float4 accesses, anything else the scalar loop: the same values up to the order of
  * the per-thread sums.  n c hw < 2^31.
  *
- * None of the three allocates or synchronises; arguments are checked before any launch. */
+ * stx_flow_compose: the per-frame set-up of the long-term consistency loss (their eq. 9 and
+ * 10) in one launch.  prev, fwd, bwd are HOST arrays of count device pointers, 1 <= count
+ * <= 4, nearest frame first: prev[q] [n][c][h][w] an earlier result, fwd[q] and bwd[q]
+ * [n][2][h][w] the flows between that frame and this one (bwd[q] maps this frame onto it).
+ * The arrays are read before the call returns and travel in the kernel's arguments: no
+ * device table, capturable.  Per pixel, for q = 0 .. count-1 in order, stx_flow_consistency's
+ * predicate is evaluated on (fwd[q], bwd[q]) (the same device function); the first q for
+ * which it holds is selected and no later offset is looked at (it reads no flow, no tap):
+ *   ref = init = stx_flow_warp's value of prev[q] along bwd[q], cmask = 1.0f, which = q.
+ * If none holds: cmask = 0.0f, which = 255, ref = +0 and init = stx_flow_warp(prev[0],
+ * bwd[0], fill).  With 0/1 masks the long-term masks max(c^j - sum_{k<j} c^k, 0) are
+ * mutually exclusive, so sum_j stx_masked_mse(x, warp_j, c_long^j) with one weight equals
+ * stx_masked_mse(x, ref, cmask).  At count = 1, (cmask, init) are stx_flow_consistency's and
+ * stx_flow_warp(fill)'s bit for bit, and ref is stx_flow_warp's under the mask.  A NaN in
+ * bwd[q] at the pixel makes offset q inconsistent there; one in prev[q] at a tap of a
+ * selected pixel makes ref and init NaN, at an unselected offset it reaches nothing.
+ * fill [n][c][h][w] is required; init and which [n][h][w] may be NULL.  ref, cmask, init
+ * must not overlap an input or each other.
+ *
+ * None of these allocates or synchronises; arguments are checked before any launch. */
+int stx_flow_compose(const float* const* prev, const float* const* fwd,
+                     const float* const* bwd, int count, const float* fill, float* ref,
+                     float* cmask, float* init, unsigned char* which, int n, int c, int h, int w,
+                     void* stream);
 int stx_flow_warp(const float* src, const float* flow, const float* fill, float* out,
                   float* valid, int n, int c, int h, int w, void* stream);
 int stx_flow_consistency(const float* fwd, const float* bwd, float* cmask, int n, int h, int w,

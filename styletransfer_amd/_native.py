@@ -208,6 +208,7 @@ SIGNATURES = {
     "stx_temporal_loss_bwd": (i32, [vp, vp, i64, vp, f32, vp, vp, i32, vp]),
     "stx_flow_warp": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "stx_flow_consistency": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "stx_flow_compose": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "stx_masked_mse_ws": (sz, []),
     "stx_masked_mse": (i32, [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, i32, vp, sz, vp]),
     "stx_flow_pyramid": (i32, [i32, i32, i32, vp, vp, i32]),

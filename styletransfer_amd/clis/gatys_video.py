@@ -22,6 +22,17 @@ def parse_flow(ctx, param, value):
     return path
 
 
+def parse_long_term(ctx, param, value):
+    """--long-term 1,2,4: the offsets of the long-term loss (video.check_offsets)."""
+    if value is None:
+        return None
+    from .. import video
+    try:
+        return video.check_offsets([int(v) for v in value.split(",")])
+    except ValueError as e:
+        raise click.BadParameter(str(e), param_hint="--long-term") from None
+
+
 @click.command()
 @click.argument("frames-path")
 @click.argument("style-image-path")
@@ -33,6 +44,11 @@ def parse_flow(ctx, param, value):
 @click.option("--save-flows", default=None, metavar="PATH.npz",
               help="With --flow auto: also write the estimated flows to this .npz, which a "
                    "later run takes as --flow")
+@click.option("--long-term", callback=parse_long_term, default=None, metavar="1,K,...",
+              help="Also tie every frame to the results K frames back, each only where all "
+                   "nearer ones are inconsistent (Ruder et al.'s long-term loss): up to 4 "
+                   "increasing offsets from 1, e.g. 1,2,4.  A flow file then also holds "
+                   "'forward_K' and 'backward_K', each [T-K, 2, S, S]; --save-flows writes them")
 @click.option("-s", "--steps", default=100, type=click.IntRange(min=0),
               help="Iterations per frame after the first")
 @click.option("--first-steps", default=None, type=click.IntRange(min=0),
@@ -52,7 +68,7 @@ def parse_flow(ctx, param, value):
               help="Multipliers of the style weight per style tap, conv1_1 .. conv3_1")
 @click.option("-o", "--out-dir", default="results/gatys_video/",
               help="Where the stylised frames 0.png, 1.png, ... are written")
-def gatys_video(frames_path, style_image_path, flow, save_flows, steps, first_steps,
+def gatys_video(frames_path, style_image_path, flow, save_flows, long_term, steps, first_steps,
                 temporal_weight, content_weight, style_weight, optimizer, layer_weights, out_dir):
     """Gatys style transfer of a clip, consistent from frame to frame.
     FRAMES_PATH: a directory of frames or a .npy array [T, H, W, 3] uint8."""
@@ -68,11 +84,18 @@ def gatys_video(frames_path, style_image_path, flow, save_flows, steps, first_st
     flows = flow
     if save_flows is not None:
         # estimated up front and handed on as explicit flows: the same bits as auto's
-        flows = video.estimate_flows(frames)
-        video.save_flows(os.path.join(root, save_flows), *flows)
+        flows = video.estimate_flows(frames, offsets=long_term or (1,))
+        if long_term in (None, (1,)):
+            video.save_flows(os.path.join(root, save_flows), *flows)
+        else:
+            video.save_flows(os.path.join(root, save_flows), *flows[1],
+                             longer={k: v for k, v in flows.items() if k > 1})
     elif flow not in ("static", "auto"):
         try:
-            flows = video.load_flows(flow, len(frames), frames[0].shape[-1])
+            if long_term is None:
+                flows = video.load_flows(flow, len(frames), frames[0].shape[-1])
+            else:
+                flows = video.load_long_flows(flow, len(frames), frames[0].shape[-1], long_term)
         except ValueError as e:
             raise click.UsageError(str(e)) from None
     style_image = img_utils.image_loader(os.path.join(root, style_image_path))
@@ -82,7 +105,7 @@ def gatys_video(frames_path, style_image_path, flow, save_flows, steps, first_st
     out = net.train_gatys_video(frames, style_image, flows, steps=steps, first_steps=first_steps,
                                 temporal_weight=temporal_weight, optimizer=optimizer,
                                 style_weight=style_weight, content_weight=content_weight,
-                                style_layer_weights=layer_weights)
+                                style_layer_weights=layer_weights, long_term=long_term)
     for i, y in enumerate(out):
         img_utils.imshow(y[0], path=os.path.join(out_dir, f"{i}.png"))
     LOGGER.info("Done! %d stylised frames have been saved to: %s", len(frames), out_dir)

@@ -11,7 +11,9 @@
 // All three are HBM / L2 streaming kernels: flow_warp moves 8 B of flow + 8 c B of taps
 // (L2 hits for a smooth flow: 4 c B from HBM) + 4 c B out per pixel, flow_consistency 24 B
 // in (bwd and its four neighbours from L2) + 4 B out, masked_mse 8 B + 4/c B in per
-// element and 8 B more with an accumulated gradient.
+// element and 8 B more with an accumulated gradient.  flow_compose is the consistency test
+// and the warp of up to four earlier frames in one pass (the long-term loss's set-up): a
+// pixel settled at the first offset moves 16 B of flows + 4 c B of taps in, 8 c + 5 B out.
 #include "common.h"
 #include "../../include/stx.h"
 
@@ -59,6 +61,16 @@ __device__ __forceinline__ bool in_range(float y, float x, int h, int w) {
   return y >= 0.f && y <= (float)(h - 1) && x >= 0.f && x <= (float)(w - 1);
 }
 
+// The source of pixel p = (i, j) along the flow f [2][hw]: y = i + dy, x = j + dx.  True and
+// the taps in t when it lies in the image; false (t untouched, no tap read) otherwise.
+__device__ __forceinline__ bool warp_taps(const float* __restrict__ f, int hw, int p, int i,
+                                          int j, int h, int w, Taps& t) {
+  const float y = (float)i + f[hw + p], x = (float)j + f[p];
+  const bool ok = in_range(y, x, h, w);
+  if (ok) t = make_taps(y, x, h, w);
+  return ok;
+}
+
 __global__ void __launch_bounds__(FB)
 flow_warp_kernel(const float* __restrict__ src, const float* __restrict__ flow,
                  const float* __restrict__ fill, float* __restrict__ out,
@@ -68,13 +80,11 @@ flow_warp_kernel(const float* __restrict__ src, const float* __restrict__ flow,
   if (p >= hw) return;
   const size_t b = blockIdx.y;
   const int i = p / w, j = p - i * w;
-  const float* f = flow + b * 2 * hw;
-  const float y = (float)i + f[hw + p], x = (float)j + f[p];
-  const bool ok = in_range(y, x, h, w);
+  Taps t;
+  const bool ok = warp_taps(flow + b * 2 * hw, hw, p, i, j, h, w, t);
   if (valid) valid[b * hw + p] = ok ? 1.f : 0.f;
   const size_t base = b * c * hw;
   if (ok) {
-    const Taps t = make_taps(y, x, h, w);
     for (int k = 0; k < c; ++k) out[base + (size_t)k * hw + p] = blend(t, src + base + (size_t)k * hw);
   } else {
     for (int k = 0; k < c; ++k) {
@@ -92,23 +102,17 @@ __device__ __forceinline__ float diff(const float* __restrict__ u, int p, int k,
   return (u[p + s] - u[p - s]) * 0.5f;
 }
 
-__global__ void __launch_bounds__(FB)
-flow_consistency_kernel(const float* __restrict__ fwd, const float* __restrict__ bwd,
-                        float* __restrict__ cmask, int h, int w) {
-  const int hw = h * w;
-  const int p = blockIdx.x * FB + threadIdx.x;
-  if (p >= hw) return;
-  const size_t b = blockIdx.y;
-  const int i = p / w, j = p - i * w;
-  const float* bu = bwd + b * 2 * hw;
+// The consistency predicate at pixel p = (i, j) of one sample (fu: fwd, bu: bwd, each
+// [2][hw]): valid and not occluded and not boundary.  t receives the taps of the pixel's
+// source along bwd whenever that source lies in the image (they are flow_warp's).
+__device__ __forceinline__ bool consistent_at(const float* __restrict__ fu,
+                                              const float* __restrict__ bu, int hw, int p, int i,
+                                              int j, int h, int w, Taps& t) {
   const float* bv = bu + hw;
   const float u = bu[p], v = bv[p];
-  const float y = (float)i + v, x = (float)j + u;
-  bool ok = in_range(y, x, h, w);
+  bool ok = warp_taps(bu, hw, p, i, j, h, w, t);
   if (ok) {
     // every comparison is false on a NaN operand: the test then does not fire
-    const Taps t = make_taps(y, x, h, w);
-    const float* fu = fwd + b * 2 * hw;
     const float wu = blend(t, fu), wv = blend(t, fu + hw);
     const float su = wu + u, sv = wv + v;
     const float m_b = u * u + v * v;
@@ -118,7 +122,72 @@ flow_consistency_kernel(const float* __restrict__ fwd, const float* __restrict__
     const bool boundary = (ux * ux + uy * uy) + (vx * vx + vy * vy) > 0.01f * m_b + 0.002f;
     ok = !occluded && !boundary;
   }
+  return ok;
+}
+
+__global__ void __launch_bounds__(FB)
+flow_consistency_kernel(const float* __restrict__ fwd, const float* __restrict__ bwd,
+                        float* __restrict__ cmask, int h, int w) {
+  const int hw = h * w;
+  const int p = blockIdx.x * FB + threadIdx.x;
+  if (p >= hw) return;
+  const size_t b = blockIdx.y;
+  const int i = p / w, j = p - i * w;
+  Taps t;
+  const bool ok = consistent_at(fwd + b * 2 * hw, bwd + b * 2 * hw, hw, p, i, j, h, w, t);
   cmask[b * hw + p] = ok ? 1.f : 0.f;
+}
+
+// Long-term consistency (Ruder et al. eq. 9, 10 with 0/1 masks): per pixel the nearest offset
+// q whose predicate holds supplies the reference.  The table of pointers travels in the
+// kernel's arguments; the loop is unrolled so that every index into it is a constant.
+constexpr int FCOMPOSE_MAX = 4;
+struct ComposeSrc {
+  const float* prev[FCOMPOSE_MAX];
+  const float* fwd[FCOMPOSE_MAX];
+  const float* bwd[FCOMPOSE_MAX];
+};
+
+__global__ void __launch_bounds__(FB)
+flow_compose_kernel(ComposeSrc a, int count, const float* __restrict__ fill,
+                    float* __restrict__ ref, float* __restrict__ cmask, float* __restrict__ init,
+                    unsigned char* __restrict__ which, int c, int h, int w) {
+  const int hw = h * w;
+  const int p = blockIdx.x * FB + threadIdx.x;
+  if (p >= hw) return;
+  const size_t b = blockIdx.y;
+  const int i = p / w, j = p - i * w;
+  const size_t fb = b * 2 * hw, base = b * c * hw;
+  Taps t;
+  const float* src = nullptr;
+  int sel = -1;
+#pragma unroll
+  for (int q = 0; q < FCOMPOSE_MAX; ++q) {
+    // a settled pixel looks at no later offset: no flow and no tap of it is read
+    if (q < count && sel < 0 && consistent_at(a.fwd[q] + fb, a.bwd[q] + fb, hw, p, i, j, h, w, t)) {
+      sel = q;
+      src = a.prev[q];
+    }
+  }
+  cmask[b * hw + p] = sel >= 0 ? 1.f : 0.f;
+  if (which) which[b * hw + p] = sel >= 0 ? (unsigned char)sel : (unsigned char)255;
+  if (sel >= 0) {
+    for (int k = 0; k < c; ++k) {
+      const size_t o = base + (size_t)k * hw + p;
+      const float v = blend(t, src + base + (size_t)k * hw);
+      ref[o] = v;
+      if (init) init[o] = v;
+    }
+  } else {
+    // no consistent source: the reference is unused (+0); the start is the nearest
+    // frame's warp where that lies in the image, the frame itself elsewhere
+    const bool ok = init && warp_taps(a.bwd[0] + fb, hw, p, i, j, h, w, t);
+    for (int k = 0; k < c; ++k) {
+      const size_t o = base + (size_t)k * hw + p;
+      ref[o] = 0.f;
+      if (init) init[o] = ok ? blend(t, a.prev[0] + base + (size_t)k * hw) : fill[o];
+    }
+  }
 }
 
 // One streaming pass: sum of mask-selected (x - ref)^2 per block, and the gradient written
@@ -216,6 +285,32 @@ extern "C" int stx_flow_consistency(const float* fwd, const float* bwd, float* c
   hipLaunchKernelGGL(flow_consistency_kernel, dim3(cdiv(h * w, FB), n), dim3(FB), 0,
                      (hipStream_t)stream, fwd, bwd, cmask, h, w);
   return check_launch("stx_flow_consistency");
+}
+
+extern "C" int stx_flow_compose(const float* const* prev, const float* const* fwd,
+                                const float* const* bwd, int count, const float* fill,
+                                float* ref, float* cmask, float* init, unsigned char* which,
+                                int n, int c, int h, int w, void* stream) {
+  bool ok = prev && fwd && bwd && count >= 1 && count <= FCOMPOSE_MAX && fill && ref && cmask &&
+            c >= 1 && flow_dims_ok(n, h, w) && ref != cmask && ref != init && cmask != init &&
+            ref != fill && init != fill && cmask != fill;
+  ComposeSrc a = {};
+  for (int q = 0; ok && q < count; ++q) {
+    a.prev[q] = prev[q];
+    a.fwd[q] = fwd[q];
+    a.bwd[q] = bwd[q];
+    for (const float* in : {prev[q], fwd[q], bwd[q]})
+      ok = ok && in && in != ref && in != cmask && in != init;
+  }
+  if (!ok) {
+    set_error("stx_flow_compose: invalid arguments (count %d n %d c %d h %d w %d; 1 <= count <= "
+              "%d, no null entry, fill given, h, w >= 2, outputs apart from the inputs)",
+              count, n, c, h, w, FCOMPOSE_MAX);
+    return STX_E_INVALID;
+  }
+  hipLaunchKernelGGL(flow_compose_kernel, dim3(cdiv(h * w, FB), n), dim3(FB), 0,
+                     (hipStream_t)stream, a, count, fill, ref, cmask, init, which, c, h, w);
+  return check_launch("stx_flow_compose");
 }
 
 extern "C" size_t stx_masked_mse_ws(void) { return FPARTS * sizeof(float); }

@@ -426,18 +426,19 @@ class StyleNetwork(nn.Module):
 
     def train_gatys_video(self, frames, style_image, flows, steps=100, first_steps=None,
                           temporal_weight=None, optimizer="adam", style_weight=100_000,
-                          content_weight=1, style_layer_weights=None):
+                          content_weight=1, style_layer_weights=None, long_term=None):
         """Temporally consistent Gatys transfer of a clip (video.gatys_video; Ruder et al.
         2016): an iterator of stylised frames.  frames: conditioned frames [1, 3, h, w];
         flows: "static", "auto" (estimated on the GPU, video.FlowEstimator) or (forward,
-        backward) at the frames' resolution."""
+        backward) at the frames' resolution.  long_term: offsets such as (1, 2, 4) of the
+        long-term loss (flows then "static", "auto" or video.load_long_flows' dict)."""
         from . import video
         tw = video.DEFAULT_TEMPORAL_WEIGHT if temporal_weight is None else temporal_weight
         return video.gatys_video(self.features(), frames, _dev(style_image), flows, steps,
                                  first_steps=first_steps, temporal_weight=tw,
                                  optimizer=optimizer, style_weight=style_weight,
                                  content_weight=content_weight,
-                                 style_layer_weights=style_layer_weights)
+                                 style_layer_weights=style_layer_weights, long_term=long_term)
 
     def train_gatys_multiscale(self, style_image, content_image, sizes, steps,
                                optimizer="lbfgs", style_weight=100_000, content_weight=1,

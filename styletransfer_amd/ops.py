@@ -23,7 +23,7 @@ __all__ = [
     "bias_grad", "gram", "style_loss", "gram_bwd", "guided_style_loss", "guided_gram_bwd", "mse", "diff_scale", "loss_combine",
     "maxpool2x2", "maxpool2x2_bwd", "relupool_bwd", "relu", "relu_bwd", "adam_step",
     "instnorm_fwd", "instnorm_bwd", "cin_mix", "upsample2x", "upsample2x_bwd", "tv_loss",
-    "temporal_loss", "temporal_loss_bwd", "flow_warp", "flow_consistency", "masked_mse",
+    "temporal_loss", "temporal_loss_bwd", "flow_warp", "flow_consistency", "flow_compose", "masked_mse",
     "color_stats", "color_affine", "resample_plan",
     "resample2d",
     "flow_pyramid", "flow_luma", "flow_linearize", "flow_jacobi", "flow_scale",
@@ -1292,6 +1292,55 @@ def flow_consistency(fwd, bwd, out=None):
     check(lib().stx_flow_consistency(fwd.data_ptr(), bwd.data_ptr(), out.data_ptr(), n, h, w,
                                      _stream()), "stx_flow_consistency")
     return out
+
+
+FLOW_COMPOSE_MAX = 4  # offsets one stx_flow_compose launch takes (include/stx.h)
+
+
+def flow_compose(prevs, fwds, bwds, fill, ref=None, cmask=None, init=None, which=None):
+    """(ref, cmask, init, which) of the long-term consistency loss in one launch
+    (stx_flow_compose): prevs, fwds, bwds are lists of 1..4 tensors, nearest frame first --
+    prevs[q] [n, c, h, w] an earlier result, (fwds[q], bwds[q]) the flows between that frame
+    and this one.  Per pixel the first q whose flow_consistency predicate holds gives
+    ref = init = flow_warp(prevs[q], bwds[q]), cmask = 1, which = q; a pixel with none has
+    cmask = 0, which = 255, ref = 0 and init = flow_warp(prevs[0], bwds[0], fill).  which is
+    uint8 [n, h, w]."""
+    count = len(prevs)
+    if not (len(fwds) == len(bwds) == count):
+        raise N.NativeError(f"flow_compose: {count} prevs, {len(fwds)} fwds, {len(bwds)} bwds")
+    if count:
+        src = _req(prevs[0], "prevs[0]")
+        if src.dim() != 4:
+            raise N.NativeError(f"prevs[0]: [n, c, h, w] required (got {tuple(src.shape)})")
+        for q in range(count):
+            _req(prevs[q], f"prevs[{q}]")
+            assert prevs[q].shape == src.shape, (q, prevs[q].shape, src.shape)
+            _flow2(bwds[q], f"bwds[{q}]", src)
+            _flow2(fwds[q], f"fwds[{q}]", src)
+    else:
+        src = _req(fill, "fill")
+    n, c, h, w = src.shape
+    if ref is None:
+        ref = torch.empty_like(src)
+    if cmask is None:
+        cmask = torch.empty((n, h, w), device=src.device, dtype=torch.float32)
+    if init is None:
+        init = torch.empty_like(src)
+    if which is None:
+        which = torch.empty((n, h, w), device=src.device, dtype=torch.uint8)
+    for t, nm in ((fill, "fill"), (ref, "ref"), (init, "init")):
+        _req(t, nm)
+        assert t.shape == src.shape, (nm, t.shape, src.shape)
+    _req(cmask, "cmask")
+    assert cmask.numel() == n * h * w, (cmask.shape, src.shape)
+    if which.dtype != torch.uint8 or not which.is_contiguous() or which.numel() != n * h * w \
+            or which.device != src.device:
+        raise N.NativeError(f"which: a contiguous uint8 [n, h, w] on {src.device} required")
+    table = lambda ts: (C.c_void_p * max(count, 1))(*[t.data_ptr() for t in ts])
+    check(lib().stx_flow_compose(table(prevs), table(fwds), table(bwds), count, fill.data_ptr(),
+                                 ref.data_ptr(), cmask.data_ptr(), init.data_ptr(),
+                                 which.data_ptr(), n, c, h, w, _stream()), "stx_flow_compose")
+    return ref, cmask, init, which
 
 
 def masked_mse(x, ref, mask, weight, out=None, add_to=None, grad=None, accumulate=False):

@@ -228,6 +228,51 @@ def process_video(net, video_path, style_name="nsp", working_dir="workdir/", out
 DEFAULT_TEMPORAL_WEIGHT = 200.0  # Ruder et al.: temporal 200 to content 1
 
 
+MAX_LONG_TERM, MAX_OFFSET = 4, 16  # offsets of one long-term loss, and the farthest of them
+
+
+def check_offsets(offsets):
+    """The offsets of a long-term loss as a tuple of ints; ValueError names the rule broken."""
+    try:
+        ks = tuple(int(k) for k in offsets)
+        if any(k != o for k, o in zip(ks, offsets)):
+            raise TypeError
+    except TypeError:
+        raise ValueError(f"long-term offsets {offsets!r}: a sequence of integers expected") \
+            from None
+    if not 1 <= len(ks) <= MAX_LONG_TERM:
+        raise ValueError(f"long-term offsets {ks}: 1 to {MAX_LONG_TERM} entries expected")
+    if ks[0] != 1:
+        raise ValueError(f"long-term offsets {ks}: the first must be 1 (the previous frame)")
+    if any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"long-term offsets {ks}: strictly increasing expected")
+    if ks[-1] > MAX_OFFSET:
+        raise ValueError(f"long-term offsets {ks}: each at most {MAX_OFFSET}")
+    return ks
+
+
+def _flow_keys(k):
+    return ("forward", "backward") if k == 1 else (f"forward_{k}", f"backward_{k}")
+
+
+def _flow_array(z, path, key, k, n_frames, size):
+    """z[key] checked as the flows of offset k of a clip of n_frames frames."""
+    a = z[key]
+    if a.dtype != np.float32:
+        raise ValueError(f"{path}: '{key}' is {a.dtype}, float32 expected")
+    if a.ndim != 4 or a.shape[1:] != (2, size, size):
+        raise ValueError(f"{path}: '{key}' has shape {a.shape}, expected "
+                         f"[T-{k}, 2, {size}, {size}] (flows at the working resolution)")
+    if a.shape[0] != max(n_frames - k, 0):
+        raise ValueError(f"{path}: '{key}' holds {a.shape[0]} flows, the clip's "
+                         f"{n_frames} frames need {max(n_frames - k, 0)}")
+    bad = int(a.size - np.isfinite(a).sum())
+    if bad:
+        raise ValueError(f"{path}: '{key}' holds {bad} non-finite values "
+                         f"({bad / a.size:.2%} of it)")
+    return np.ascontiguousarray(a)
+
+
 def load_flows(path, n_frames, size):
     """(forward, backward) of an .npz: float32 arrays [n_frames - 1, 2, size, size] at the
     working resolution -- the flows between the conditioned frames (after centre crop and
@@ -239,31 +284,44 @@ def load_flows(path, n_frames, size):
         for key in ("forward", "backward"):
             if key not in z.files:
                 raise ValueError(f"{path}: no '{key}' array (found {sorted(z.files)})")
-            a = z[key]
-            if a.dtype != np.float32:
-                raise ValueError(f"{path}: '{key}' is {a.dtype}, float32 expected")
-            if a.ndim != 4 or a.shape[1:] != (2, size, size):
-                raise ValueError(f"{path}: '{key}' has shape {a.shape}, expected "
-                                 f"[T-1, 2, {size}, {size}] (flows at the working resolution)")
-            if a.shape[0] != n_frames - 1:
-                raise ValueError(f"{path}: '{key}' holds {a.shape[0]} flows, the clip's "
-                                 f"{n_frames} frames need {n_frames - 1}")
-            bad = int(a.size - np.isfinite(a).sum())
-            if bad:
-                raise ValueError(f"{path}: '{key}' holds {bad} non-finite values "
-                                 f"({bad / a.size:.2%} of it)")
-            out.append(np.ascontiguousarray(a))
+            out.append(_flow_array(z, path, key, 1, n_frames, size))
     return out[0], out[1]
 
 
-def save_flows(path, forward, backward):
+def load_long_flows(path, n_frames, size, offsets):
+    """{k: (forward_k, backward_k)} of an .npz for the offsets of a long-term loss: key 1 is
+    load_flows' pair, key k > 1 the arrays 'forward_k' and 'backward_k', float32
+    [n_frames - k, 2, size, size]: forward_k[t-k] maps frame t-k onto frame t, backward_k[t-k]
+    frame t onto frame t-k.  ValueError names what is wrong with a file that does not fit."""
+    out = {}
+    with np.load(path, allow_pickle=False) as z:
+        for k in check_offsets(offsets):
+            pair = []
+            for key in _flow_keys(k):
+                if key not in z.files:
+                    hint = "" if k == 1 else (f" for offset {k}: `--flow auto --save-flows` with "
+                                              "these --long-term offsets writes it")
+                    raise ValueError(f"{path}: no '{key}' array{hint} (found {sorted(z.files)})")
+                pair.append(_flow_array(z, path, key, k, n_frames, size))
+            out[k] = tuple(pair)
+    return out
+
+
+def save_flows(path, forward, backward, longer=None):
     """Write the .npz that load_flows reads: float32 'forward' and 'backward', each
-    [T-1, 2, S, S]."""
-    f, b = (np.ascontiguousarray(a, dtype=np.float32) for a in (forward, backward))
-    if f.shape != b.shape or f.ndim != 4 or f.shape[1] != 2:
-        raise ValueError(f"flows [T-1, 2, h, w] of one shape expected (got {f.shape}, {b.shape})")
+    [T-1, 2, S, S].  longer: {k: (forward_k, backward_k)}, k > 1, each [T-k, 2, S, S], written
+    as 'forward_k' and 'backward_k' (load_long_flows reads them)."""
+    arrays = {}
+    for k, (fk, bk) in sorted({1: (forward, backward), **(longer or {})}.items()):
+        f, b = (np.ascontiguousarray(a, dtype=np.float32) for a in (fk, bk))
+        if f.shape != b.shape or f.ndim != 4 or f.shape[1] != 2:
+            raise ValueError(f"flows [T-{k}, 2, h, w] of one shape expected (got {f.shape}, "
+                             f"{b.shape})")
+        if longer and (int(k) != k or not 1 <= k <= MAX_OFFSET):
+            raise ValueError(f"offset {k!r}: an integer in 1..{MAX_OFFSET} expected")
+        arrays.update(zip(_flow_keys(int(k)), (f, b)))
     with open(path, "wb") as fh:  # (a file object: numpy appends no second .npz to the name)
-        np.savez(fh, forward=f, backward=b)
+        np.savez(fh, **arrays)
 
 
 class FlowEstimator:
@@ -274,78 +332,183 @@ class FlowEstimator:
     (channel 0 = dx, 1 = dy, in pixels; bwd maps cur onto prev): both directions run as one
     batch of two.  Every level's buffers and the resample tables are made here; pair
     allocates nothing, synchronises nothing and can be captured (ops.graph_capture).  The
-    estimator holds no graph: whoever captures pair owns the graph."""
+    estimator holds no graph: whoever captures pair owns the graph.
+
+    pairs=P: buffers for P frame pairs, batch 2 P.  pairs_flow([(a_0, b_0), ...]) takes 1..P
+    pairs and estimates them all in one sequence of launches (every kernel takes a batch;
+    samples are independent, so a pair's flows are pair(a_q, b_q)'s bit for bit); a shorter
+    list uses the leading part of the batch.  It returns static views [(fwd_q, bwd_q)]."""
 
     def __init__(self, h, w, device=None, alpha=15.0, warps=5, iters=40, min_side=16,
-                 mean=None, std=None):
+                 mean=None, std=None, pairs=1):
         if warps < 1 or iters < 1:
             raise ValueError(f"warps {warps}, iters {iters}: at least 1 each")
+        if pairs < 1:
+            raise ValueError(f"pairs {pairs}: at least 1")
         self.dev = torch.device(device or constants.DEVICE)
         self.alpha, self.warps, self.iters = float(alpha), int(warps), int(iters)
         self.mean, self.std = mean, std
+        self.pairs = int(pairs)
         self.levels = ops.flow_pyramid(h, w, min_side)
         z = lambda *s: torch.zeros(s, device=self.dev, dtype=torch.float32)
-        # per level: luma [A | B] = [(prev, cur) | (cur, prev)], two flow buffers, coefficients
-        self.grey = [z(2, 2, hl, wl) for hl, wl in self.levels]
-        self.uv = [(z(2, 2, hl, wl), z(2, 2, hl, wl)) for hl, wl in self.levels]
-        self.coef = [z(2, 3, hl, wl) for hl, wl in self.levels]
+        nb = 2 * self.pairs
+        # per level: luma [A | B], pair q in samples 2q, 2q+1 = [(prev, cur) | (cur, prev)],
+        # two flow buffers, coefficients
+        self.grey = [z(2, nb, hl, wl) for hl, wl in self.levels]
+        self.uv = [(z(nb, 2, hl, wl), z(nb, 2, hl, wl)) for hl, wl in self.levels]
+        self.coef = [z(nb, 3, hl, wl) for hl, wl in self.levels]
         # level 0 starts in the buffer from which `warps` swaps end in uv[0][0]
         self.flow = self.uv[0][0]
-        self.fwd, self.bwd = self.flow[0:1], self.flow[1:2]
-        self.pair(z(1, 3, h, w), z(1, 3, h, w))  # uploads the tables, sizes the scratch
+        self.views = [(self.flow[2 * q:2 * q + 1], self.flow[2 * q + 1:2 * q + 2])
+                      for q in range(self.pairs)]
+        self.fwd, self.bwd = self.views[0]
+        blank = z(1, 3, h, w)
+        self.pairs_flow([(blank, blank)] * self.pairs)  # uploads the tables, sizes the scratch
         torch.cuda.synchronize(self.dev)
 
     def pair(self, prev, cur):
+        return self.pairs_flow([(prev, cur)])[0]
+
+    def pairs_flow(self, pairs):
+        m = len(pairs)
+        if not 1 <= m <= self.pairs:
+            raise ValueError(f"pairs_flow: {m} pairs, this estimator takes 1..{self.pairs}")
+        nb, whole = 2 * m, m == self.pairs
         g0 = self.grey[0]
-        for img, a_slot, b_slot in ((prev, 0, 1), (cur, 1, 0)):
-            ops.flow_luma(img, self.mean, self.std, out=g0[0, a_slot:a_slot + 1])
-            ops.flow_luma(img, self.mean, self.std, out=g0[1, b_slot:b_slot + 1])
+        for q, (prev, cur) in enumerate(pairs):
+            for img, a_slot, b_slot in ((prev, 2 * q, 2 * q + 1), (cur, 2 * q + 1, 2 * q)):
+                ops.flow_luma(img, self.mean, self.std, out=g0[0, a_slot:a_slot + 1])
+                ops.flow_luma(img, self.mean, self.std, out=g0[1, b_slot:b_slot + 1])
         for l in range(1, len(self.levels)):
-            ops.resample2d(self.grey[l - 1], self.levels[l], "triangle", out=self.grey[l])
+            if whole:
+                ops.resample2d(self.grey[l - 1], self.levels[l], "triangle", out=self.grey[l])
+            else:  # the leading samples of A and of B are two contiguous runs
+                for s in (0, 1):
+                    ops.resample2d(self.grey[l - 1][s, :nb], self.levels[l], "triangle",
+                                   out=self.grey[l][s, :nb])
         top = len(self.levels) - 1
         for l in range(top, -1, -1):
             hl, wl = self.levels[l]
             # `warps` swaps must end in buffer 0 (level 0: the static output)
             src = self.warps % 2
+            uv = [u[:nb] for u in self.uv[l]]
+            coef, a, b = self.coef[l][:nb], self.grey[l][0, :nb], self.grey[l][1, :nb]
             if l == top:
-                self.uv[l][src].zero_()
+                uv[src].zero_()
             else:
                 hc, wc = self.levels[l + 1]
-                ops.resample2d(self.uv[l + 1][0], (hl, wl), "triangle", out=self.uv[l][src])
-                ops.flow_scale(self.uv[l][src], np.float32(wl) / np.float32(wc),
+                ops.resample2d(self.uv[l + 1][0][:nb], (hl, wl), "triangle", out=uv[src])
+                ops.flow_scale(uv[src], np.float32(wl) / np.float32(wc),
                                np.float32(hl) / np.float32(hc))
             for _ in range(self.warps):
-                cur_uv, nxt = self.uv[l][src], self.uv[l][src ^ 1]
-                ops.flow_linearize(self.grey[l][0], self.grey[l][1], cur_uv, out=self.coef[l])
-                ops.flow_jacobi(self.coef[l], cur_uv, out=nxt, alpha=self.alpha, iters=self.iters)
+                ops.flow_linearize(a, b, uv[src], out=coef)
+                ops.flow_jacobi(coef, uv[src], out=uv[src ^ 1], alpha=self.alpha,
+                                iters=self.iters)
                 src ^= 1
-        return self.fwd, self.bwd
+        return self.views[:m]
 
 
-def estimate_flows(frames, device=None, **params):
+def estimate_flows(frames, device=None, offsets=(1,), **params):
     """(forward, backward) of a clip's conditioned frames [1, 3, S, S]: float32 arrays
-    [T-1, 2, S, S], what load_flows returns (FlowEstimator; params: its keywords)."""
+    [T-1, 2, S, S], what load_flows returns (FlowEstimator; params: its keywords).
+    offsets other than (1,): {k: (forward_k, backward_k)}, each [T-k, 2, S, S], what
+    load_long_flows returns -- per frame one pairs_flow call over its offsets, the flows
+    that gatys_video(..., "auto", long_term=offsets) estimates."""
     dev = torch.device(device or constants.DEVICE)
-    est, prev, fwd, bwd = None, None, [], []
+    offsets = check_offsets(offsets)
+    est, past = None, []  # past: the last max(offsets) frames, nearest first
+    found = {k: ([], []) for k in offsets}
     for frame in frames:
         frame = frame.to(dev, torch.float32).contiguous()
         if est is None:
-            est = FlowEstimator(frame.shape[-2], frame.shape[-1], dev, **params)
-        if prev is not None:
-            f, b = est.pair(prev, frame)
-            fwd.append(f[0].cpu().numpy())
-            bwd.append(b[0].cpu().numpy())
-        prev = frame
+            est = FlowEstimator(frame.shape[-2], frame.shape[-1], dev, pairs=len(offsets),
+                                **params)
+        ks = [k for k in offsets if k <= len(past)]
+        if ks:
+            for k, (f, b) in zip(ks, est.pairs_flow([(past[k - 1], frame) for k in ks])):
+                found[k][0].append(f[0].cpu().numpy())
+                found[k][1].append(b[0].cpu().numpy())
+        past = [frame] + past[:offsets[-1] - 1]
     if est is None:
         raise ValueError("estimate_flows: no frames")
-    shape = (0, 2) + tuple(prev.shape[-2:])
-    return (np.stack(fwd) if fwd else np.zeros(shape, np.float32),
-            np.stack(bwd) if bwd else np.zeros(shape, np.float32))
+    shape = (0, 2) + tuple(past[0].shape[-2:])
+    stack = lambda a: np.stack(a) if a else np.zeros(shape, np.float32)
+    out = {k: (stack(f), stack(b)) for k, (f, b) in found.items()}
+    return out[1] if offsets == (1,) else out
+
+
+def _gatys_video_long(feat, frames, flows, steps, first_steps, temporal_weight, optimizer,
+                      offsets, kw, lr):
+    """gatys_video with the long-term loss over `offsets` (see there)."""
+    from . import vgg as V
+    dev = feat.device
+    static, auto = flows == "static", flows == "auto"
+    if not (static or auto):
+        if not isinstance(flows, dict):  # (forward, backward): the offset-1 flows
+            flows = {1: tuple(flows)}
+        missing = [k for k in offsets if k not in flows]
+        if missing:
+            raise ValueError(f"long_term {offsets}: no flows given for offsets {missing}")
+    K = offsets[-1]
+    est = eng = results = seen = omega = init = cmask = zero = which = None
+    for t, frame in enumerate(frames):
+        frame = frame.to(dev, torch.float32).contiguous()
+        if t == 0:
+            n, _, h, w = frame.shape
+            # rings of the last K results (for auto also of the frames): frame t in slot t % K
+            results = [torch.empty_like(frame) for _ in range(K)]
+            seen = [torch.empty_like(frame) for _ in range(K)] if auto else None
+            omega, init = torch.empty_like(frame), torch.empty_like(frame)
+            cmask = torch.zeros((n, h, w), device=dev, dtype=torch.float32)
+            zero = torch.zeros((n, 2, h, w), device=dev, dtype=torch.float32)
+            which = torch.empty((n, h, w), device=dev, dtype=torch.uint8)
+            omega.copy_(frame)  # frame 0: an all-zero mask, the term is exactly 0
+            if optimizer == "adam":
+                eng = V.GatysEngine(feat, None, frame, lr=lr,
+                                    temporal=(omega, cmask, temporal_weight), **kw)
+            else:
+                eng = V.GatysLBFGS(feat, None, frame, **kw)
+            eng.run(first_steps)
+        else:
+            ks = [k for k in offsets if t - k >= 0]
+            if static:
+                pairs = [(zero, zero)] * len(ks)
+            elif auto:
+                if est is None:
+                    est = FlowEstimator(h, w, dev, pairs=len(offsets))
+                pairs = est.pairs_flow([(seen[(t - k) % K], frame) for k in ks])
+            else:
+                pairs = []
+                for k in ks:
+                    if t - k >= len(flows[k][0]):
+                        raise ValueError(f"frame {t}: only {len(flows[k][0])} flows of offset "
+                                         f"{k} given")
+                    pairs.append(tuple(torch.as_tensor(f[t - k]).to(dev, torch.float32)
+                                       .reshape(zero.shape).contiguous() for f in flows[k]))
+            ops.flow_compose([results[(t - k) % K] for k in ks], [f for f, _ in pairs],
+                             [b for _, b in pairs], frame, ref=omega, cmask=cmask, init=init,
+                             which=which)
+            if optimizer == "adam":
+                eng.retarget(frame, init=init, temporal_ref=omega, temporal_mask=cmask)
+                if eng.graph is None:
+                    eng.run(steps)
+                else:
+                    for _ in range(steps):
+                        eng.graph.replay()
+            else:
+                eng = V.GatysLBFGS(feat, None, frame, init=init,
+                                   temporal=(omega, cmask, temporal_weight), **kw)
+                eng.run(steps)
+        results[t % K].copy_(eng.x.detach())
+        if auto:
+            seen[t % K].copy_(frame)
+        yield results[t % K].clone()
 
 
 def gatys_video(feat, frames, style_image, flows, steps, first_steps=None,
                 temporal_weight=DEFAULT_TEMPORAL_WEIGHT, optimizer="adam", style_weight=100_000,
-                content_weight=1, style_layer_weights=None, lr=1e-3) -> Iterator[torch.Tensor]:
+                content_weight=1, style_layer_weights=None, lr=1e-3,
+                long_term=None) -> Iterator[torch.Tensor]:
     """Stylised frames [1, 3, h, w] of a clip, one Gatys optimisation per frame (Ruder,
     Dosovitskiy & Brox 2016, short-term consistency).  frames: conditioned frames, as
     iterate_frames yields them; flows: "static" (a fixed camera: zero flow both ways), "auto"
@@ -359,8 +522,19 @@ def gatys_video(feat, frames, style_image, flows, steps, first_steps=None,
 
     to the Gatys loss.  optimizer "adam": one engine, captured once and moved from frame to
     frame (GatysEngine.retarget), steps = iterations; "lbfgs": a GatysLBFGS per frame,
-    steps = outer steps."""
+    steps = outer steps.
+
+    long_term: None, or offsets such as (1, 2, 4) (strictly increasing from 1, at most 4, each
+    <= 16; check_offsets): Ruder et al.'s long-term loss (eq. 9, 10).  Frame t is tied to
+    the results t-k, each farther one only where every nearer one is inconsistent.  With 0/1
+    masks and one weight that sum is the same masked loss on a composed reference and mask,
+    which one ops.flow_compose per frame builds over the offsets with t - k >= 0 (DESIGN.md
+    3.9): the engine, its graph and retarget are the short-term ones.  flows is then "static",
+    "auto" (one FlowEstimator.pairs_flow per frame over (frame t-k, frame t)) or a dict
+    {k: (forward_k, backward_k)} (load_long_flows): forward_k[t-k] maps frame t-k onto t."""
     from . import vgg as V
+    if long_term is not None:
+        long_term = check_offsets(long_term)
     if optimizer not in ("adam", "lbfgs"):
         raise ValueError(f"optimizer {optimizer!r}: 'adam' or 'lbfgs'")
     dev = feat.device
@@ -372,6 +546,10 @@ def gatys_video(feat, frames, style_image, flows, steps, first_steps=None,
     targets = feat.style_targets(style_image.to(dev, torch.float32))
     kw = dict(style_weight=style_weight, content_weight=content_weight, targets=targets,
               style_layer_weights=style_layer_weights)
+    if long_term is not None:
+        yield from _gatys_video_long(feat, frames, flows, steps, first_steps, temporal_weight,
+                                     optimizer, long_term, kw, lr)
+        return
     eng = prev = omega = init = cmask = zero = None
     for t, frame in enumerate(frames):
         frame = frame.to(dev, torch.float32).contiguous()

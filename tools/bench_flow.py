@@ -11,9 +11,13 @@ One GPU, one process; the batch is 2 (both directions of a pair), --sizes square
              device synchronise: the launches' host cost included) and as one captured graph
              replayed, us per frame pair; and the number of kernel launches of a pair.
 
+  pairs      with --pairs P > 1: FlowEstimator(pairs=P).pairs_flow over P frame pairs (one
+             sequence of launches, batch 2 P) against P pair calls of a one-pair estimator,
+             eager and replayed, alternating windows, us per P pairs.
+
 Prints one JSON line, with the box's calibration (bench.py's `box` block) taken first.
 
-    python tools/bench_flow.py [--sizes 512,32] [--iters 40]
+    python tools/bench_flow.py [--sizes 512,32] [--iters 40] [--pairs 3]
 """
 import argparse
 import json
@@ -38,6 +42,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="replays per window")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--no-box", action="store_true", help="skip the box calibration")
+    ap.add_argument("--pairs", type=int, default=1,
+                    help="also time pairs_flow over this many pairs against as many pair calls")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_flow: needs a GPU (there is no CPU path to time)")
@@ -70,6 +76,19 @@ def main():
             per = lambda hw: 1 if max(hw) <= 32 else -(-est.iters // N.STX_FLOW_JACOBI_MAXFUSE)
             r["pair_launches"] = 4 + 2 * (len(est.levels) - 1) + 3 * (len(est.levels) - 1) + 1 + \
                 sum(est.warps * (1 + per(hw)) for hw in est.levels)
+            if a.pairs > 1:
+                batched = video.FlowEstimator(S, S, dev, pairs=a.pairs)
+                frames = [torch.randn(1, 3, S, S, device=dev) for _ in range(a.pairs)]
+                many = lambda: batched.pairs_flow([(f, c) for f in frames])
+
+                def separate():
+                    for f in frames:
+                        est.pair(f, c)
+                gm, gs = graph_of(many, 1), graph_of(separate, 1)
+                r["pairs_us"] = compare({"batched_eager": many, "separate_eager": separate,
+                                         "batched_replayed": gm.replay,
+                                         "separate_replayed": gs.replay}, a.steps, 3, a.rounds, 1e6)
+                r["pairs"] = a.pairs
         res["sizes"][str(S)] = r
     print(json.dumps(res))
 
