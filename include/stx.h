@@ -583,9 +583,16 @@ int stx_adam_step_clear(float* p, const float* g, float* m, float* v, long long 
 
 /* InstanceNorm2d(affine) forward, per (n,c) plane over hw (biased var, eps):
  *   u = x (+ res);  y = (u-mean)*rstd*gamma + beta, formed as fma(u, gsc, sh) with
- *   gsc = gamma rstd, sh = fma(-mean, gsc, beta);  y = max(y,0) if relu.
+ *   gsc = gamma rstd, sh = fma(-mean, gsc, beta);  y = (y <= 0 ? +0 : y) if relu.
  * mean/rstd [n*c] saved for the backward (may be NULL).  out_amax (amax group, zeroed
- * by the caller, may be NULL) receives max|y| -- the next split conv's input scale. */
+ * by the caller, may be NULL) receives max|y| -- the next split conv's input scale.
+ * x, res and y must be 16-byte aligned (STX_E_INVALID otherwise).
+ * A NaN or Inf anywhere in a plane of u makes that plane's mean NaN (Inf for +-Inf
+ * alone), its rstd, gsc and sh NaN and so every y of the plane, with relu too: the ReLU
+ * keeps a NaN, as torch's and stx_relu_fwd (fmaxf(NaN, 0) = 0 would hand on a clean
+ * zero plane with out_amax = 0), and out_amax then holds a NaN.  The other planes of the call
+ * are untouched, bit for bit.  The 64^2 planes that share a block (n*c a multiple of 4,
+ * from 1024 planes) have the bits of the same planes computed one per block. */
 int stx_instnorm_fwd(const float* x, const float* res, const float* gamma, const float* beta,
                      float* y, float* mean, float* rstd, int n, int c, int hw, float eps,
                      int relu, float* out_amax, void* stream);
@@ -596,7 +603,14 @@ int stx_instnorm_fwd(const float* x, const float* res, const float* gamma, const
  * (may be NULL) (+)= sum_{n,p} du: the bias gradient of the conv that produced x
  * (stransfer/network.py:471-611, every Conv2d followed by InstanceNorm2d), so that
  * conv needs no separate bias-gradient pass.  out_amax (amax group or NULL) receives
- * max|du| -- the split dgrad/wgrad scale of du. */
+ * max|du| -- the split dgrad/wgrad scale of du.
+ * A NaN in dy of a plane (at an element the ReLU lets through) makes the plane's sums
+ * NaN and so its whole du, its three partials, its channel of dgamma / dbeta / dbias_in
+ * and out_amax; the other planes and channels are untouched, bit for bit.  A NaN (or
+ * Inf) in x reaches the backward through the saved mean / rstd, both NaN: the recomputed
+ * mask !(NaN > 0) zeroes g on the whole plane, but k = gamma rstd / hw is NaN and every
+ * du of the plane is NaN, with and without relu (not 0, unlike stx_relu_bwd at a NaN y:
+ * the plane has no finite statistics to differentiate through). */
 size_t stx_instnorm_bwd_ws(int n, int c);
 /* The parameter reductions of many stx_instnorm_bwd calls in one launch: each such
  * call ran with dgamma = dbeta = dbias_in = NULL into its own workspace `parts`

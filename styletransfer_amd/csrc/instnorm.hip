@@ -6,9 +6,9 @@
 // biased variance, per-instance statistics in train and eval, no running stats),
 // residual `out += residual` (stransfer/network.py:502) and nn.ReLU.
 //
-// One 256-thread block per (n, c) plane.  Forward: u = x (+ res); two passes
-// over u (mean, then sum of squared deviations: numerically like torch's
-// two-pass CPU kernel), then y = (u-mean)*rstd*gamma + beta (relu).  The plane
+// One block per (n, c) plane (256 threads; 1024 from 16 K floats).  Forward: u = x
+// (+ res); two passes over u (mean, then sum of squared deviations: numerically like
+// torch's two-pass CPU kernel), then y = (u-mean)*rstd*gamma + beta (relu).  The plane
 // (<= 256 KB at 256x256) stays L2-resident between the passes.
 #include "common.h"
 #include "conv_epi.h"
@@ -28,13 +28,26 @@ __device__ __forceinline__ void in_coefs(const float* gamma, const float* beta, 
   sh = __builtin_fmaf(-mean, gsc, beta ? beta[ch] : 0.f);
 }
 
-__global__ void __launch_bounds__(NB)
+// the forward's ReLU keeps a NaN (a NaN or Inf in a plane makes its mean, gsc, sh and so
+// every y NaN): fmaxf(NaN, 0) = 0 would hand on a clean zero plane with out_amax = 0.
+// stx_relu_fwd's form; a backward's !(fma > 0) reads the same NaN as "not positive"
+__device__ __forceinline__ float in_relu(float o) { return o <= 0.f ? 0.f : o; }
+
+// the squared deviations of one float4 group, with the fmas written out: left to the
+// compiler, a*a + b*b came out fused in the pipelined kernel and unfused in the one-plane
+// register kernels (13 of 1024 planes with another rstd), against "the same bits" below
+__device__ __forceinline__ float sq4(const f32x4& d) {
+  return __builtin_fmaf(d[0], d[0], d[1] * d[1]) + __builtin_fmaf(d[2], d[2], d[3] * d[3]);
+}
+
+template <int NBT>
+__global__ void __launch_bounds__(NBT)
 instnorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
                     const float* __restrict__ gamma, const float* __restrict__ beta,
                     float* __restrict__ y, float* __restrict__ mean_out,
                     float* __restrict__ rstd_out, int c, int hw, float eps, int relu,
                     float* __restrict__ out_amax) {
-  __shared__ float red[NB / 64];
+  __shared__ float red[NBT / 64];
   const size_t base = (size_t)blockIdx.x * hw;
   const int ch = blockIdx.x % c;
   const float* xp = x + base;
@@ -42,52 +55,52 @@ instnorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
   const bool vec = ((hw & 3) == 0);
   float s = 0.f;
   if (vec) {
-    for (int i = threadIdx.x * 4; i < hw; i += NB * 4) {
+    for (int i = threadIdx.x * 4; i < hw; i += NBT * 4) {
       f32x4 v = *reinterpret_cast<const f32x4*>(xp + i);
       if (rp) v += *reinterpret_cast<const f32x4*>(rp + i);
       s += (v[0] + v[1]) + (v[2] + v[3]);
     }
   } else {
-    for (int i = threadIdx.x; i < hw; i += NB) s += xp[i] + (rp ? rp[i] : 0.f);
+    for (int i = threadIdx.x; i < hw; i += NBT) s += xp[i] + (rp ? rp[i] : 0.f);
   }
-  const float mean = block_sum<NB>(s, red) / (float)hw;
+  const float mean = block_sum<NBT>(s, red) / (float)hw;
   float q = 0.f;
   if (vec) {
-    for (int i = threadIdx.x * 4; i < hw; i += NB * 4) {
+    for (int i = threadIdx.x * 4; i < hw; i += NBT * 4) {
       f32x4 v = *reinterpret_cast<const f32x4*>(xp + i);
       if (rp) v += *reinterpret_cast<const f32x4*>(rp + i);
       v -= mean;
-      q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+      q += sq4(v);
     }
   } else {
-    for (int i = threadIdx.x; i < hw; i += NB) {
+    for (int i = threadIdx.x; i < hw; i += NBT) {
       const float d = xp[i] + (rp ? rp[i] : 0.f) - mean;
       q += d * d;
     }
   }
-  const float var = block_sum<NB>(q, red) / (float)hw;
+  const float var = block_sum<NBT>(q, red) / (float)hw;
   const float rstd = 1.f / sqrtf(var + eps);
   float gsc, sh;
   in_coefs(gamma, beta, ch, mean, rstd, gsc, sh);
   float* yp = y + base;
   uint32_t om = 0u;  // max |y| as IEEE bits (NaN sorts above inf)
   if (vec) {
-    for (int i = threadIdx.x * 4; i < hw; i += NB * 4) {
+    for (int i = threadIdx.x * 4; i < hw; i += NBT * 4) {
       f32x4 v = *reinterpret_cast<const f32x4*>(xp + i);
       if (rp) v += *reinterpret_cast<const f32x4*>(rp + i);
       f32x4 o;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         o[k] = __builtin_fmaf(v[k], gsc, sh);
-        if (relu) o[k] = fmaxf(o[k], 0.f);
+        if (relu) o[k] = in_relu(o[k]);
         om = max(om, __float_as_uint(o[k]) & 0x7fffffffu);
       }
       *reinterpret_cast<f32x4*>(yp + i) = o;
     }
   } else {
-    for (int i = threadIdx.x; i < hw; i += NB) {
+    for (int i = threadIdx.x; i < hw; i += NBT) {
       float o = __builtin_fmaf(xp[i] + (rp ? rp[i] : 0.f), gsc, sh);
-      o = relu ? fmaxf(o, 0.f) : o;
+      o = relu ? in_relu(o) : o;
       yp[i] = o;
       om = max(om, __float_as_uint(o) & 0x7fffffffu);
     }
@@ -102,6 +115,17 @@ instnorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
 // Backward.  g = dy * (y > 0 if relu);  xh = (u-mean)*rstd
 //   dgamma_nc = sum g*xh ; dbeta_nc = sum g
 //   du = gamma*rstd/HW * (HW*g - dbeta_nc - xh*dgamma_nc)
+// sgx accumulates as fma(g, xh, sgx) and du is formed by in_du, both with the fmas written
+// out in every backward kernel: left to the compiler, the pipelined kernel and the
+// one-plane kernels contracted these differently (du of the same plane a rounding apart).
+// The last product is not to be contracted either: sum du adds the du that is stored, not
+// fma(k, ., sum) in one kernel and the rounded product in another
+__device__ __forceinline__ float in_du(float k, float fhw, float g, float sg, float xh,
+                                       float sgx) {
+#pragma clang fp contract(off)
+  return k * __builtin_fmaf(-xh, sgx, __builtin_fmaf(fhw, g, -sg));
+}
+
 // max |.| over an NT-thread block, then one atomic into slot (block id & 31)
 template <int NT>
 __device__ __forceinline__ void block_max_to_nt(float* group, uint32_t mu, float* red) {
@@ -153,7 +177,7 @@ instnorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ beta
         const float g = (relu && !(__builtin_fmaf(u, gsc, sh) > 0.f)) ? 0.f : d4[e];
         const float xh = (u - mu) * rs;
         sg += g;
-        sgx += g * xh;
+        sgx = __builtin_fmaf(g, xh, sgx);
       }
     }
   } else {
@@ -163,7 +187,7 @@ instnorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ beta
       if (relu && !(__builtin_fmaf(u, gsc, sh) > 0.f)) g = 0.f;
       const float xh = (u - mu) * rs;
       sg += g;
-      sgx += g * xh;
+      sgx = __builtin_fmaf(g, xh, sgx);
     }
   }
   sg = block_sum<NBT>(sg, red);
@@ -184,7 +208,7 @@ instnorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ beta
         const float u = x4[e] + r4[e];
         const float g = (relu && !(__builtin_fmaf(u, gsc, sh) > 0.f)) ? 0.f : d4[e];
         const float xh = (u - mu) * rs;
-        o[e] = k * ((float)hw * g - sg - xh * sgx);
+        o[e] = in_du(k, (float)hw, g, sg, xh, sgx);
         om = max(om, __float_as_uint(o[e]) & 0x7fffffffu);
         sdu += o[e];
       }
@@ -196,7 +220,7 @@ instnorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ beta
       const float u = xp[i] + (rp ? rp[i] : 0.f);
       if (relu && !(__builtin_fmaf(u, gsc, sh) > 0.f)) g = 0.f;
       const float xh = (u - mu) * rs;
-      const float o = k * ((float)hw * g - sg - xh * sgx);
+      const float o = in_du(k, (float)hw, g, sg, xh, sgx);
       dup[i] = o;
       om = max(om, __float_as_uint(o) & 0x7fffffffu);
       sdu += o;
@@ -258,7 +282,7 @@ instnorm_fwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ r
   for (int k = 0; k < R4; ++k) {
     if (threadIdx.x + k * NT < n4) {
       const f32x4 d = u[k] - mean;
-      q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+      q += sq4(d);
     }
   }
   const float var = block_sum_nt<NT>(q, red) / (float)hw;
@@ -275,7 +299,7 @@ instnorm_fwd_reg_kernel(const float* __restrict__ x, const float* __restrict__ r
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         o[e] = __builtin_fmaf(u[k][e], gsc, sh);
-        if (relu) o[e] = fmaxf(o[e], 0.f);
+        if (relu) o[e] = in_relu(o[e]);
         om = max(om, __float_as_uint(o[e]) & 0x7fffffffu);
       }
       yp[i] = o;
@@ -340,7 +364,7 @@ instnorm_bwd_reg_kernel(const float* __restrict__ dy, const float* __restrict__ 
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       sg += g[k][e];
-      sgx += g[k][e] * xh[k][e];
+      sgx = __builtin_fmaf(g[k][e], xh[k][e], sgx);
     }
   sg = block_sum_nt<NT>(sg, red);
   sgx = block_sum_nt<NT>(sgx, red);
@@ -356,7 +380,7 @@ instnorm_bwd_reg_kernel(const float* __restrict__ dy, const float* __restrict__ 
       f32x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        o[e] = kk * ((float)hw * g[k][e] - sg - xh[k][e] * sgx);
+        o[e] = in_du(kk, (float)hw, g[k][e], sg, xh[k][e], sgx);
         om = max(om, __float_as_uint(o[e]) & 0x7fffffffu);
       }
       dup[i] = o;
@@ -437,7 +461,7 @@ instnorm_fwd_pipe_kernel(const float* __restrict__ x, const float* __restrict__ 
 #pragma unroll
     for (int k = 0; k < R4; ++k) {
       const f32x4 d = u[k] - mean;
-      q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+      q += sq4(d);
     }
     const float var = block_sum_nt<NT>(q, red) / (float)HW;
     const float rstd = 1.f / sqrtf(var + eps);
@@ -451,7 +475,7 @@ instnorm_fwd_pipe_kernel(const float* __restrict__ x, const float* __restrict__ 
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         o[e] = __builtin_fmaf(u[k][e], gsc, sh);
-        if (relu) o[e] = fmaxf(o[e], 0.f);
+        if (relu) o[e] = in_relu(o[e]);
         om = max(om, __float_as_uint(o[e]) & 0x7fffffffu);
       }
       yp[threadIdx.x + k * NT] = o;
@@ -525,7 +549,7 @@ instnorm_bwd_pipe_kernel(const float* __restrict__ dy, const float* __restrict__
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         sg += g[k][e];
-        sgx += g[k][e] * xh[k][e];
+        sgx = __builtin_fmaf(g[k][e], xh[k][e], sgx);
       }
     sg = block_sum_nt<NT>(sg, red);
     sgx = block_sum_nt<NT>(sgx, red);
@@ -538,7 +562,7 @@ instnorm_bwd_pipe_kernel(const float* __restrict__ dy, const float* __restrict__
       f32x4 o;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        o[e] = kk * ((float)HW * g[k][e] - sg - xh[k][e] * sgx);
+        o[e] = in_du(kk, (float)HW, g[k][e], sg, xh[k][e], sgx);
         om = max(om, __float_as_uint(o[e]) & 0x7fffffffu);
       }
       dup[threadIdx.x + k * NT] = o;
@@ -612,7 +636,7 @@ instnorm_bwd_greg_kernel(const float* __restrict__ dy, const float* __restrict__
       g[k][e] = !(__builtin_fmaf(u4[e], gsc, sh) > 0.f) ? 0.f : d4[e];
       const float xh = in ? (u4[e] - mu) * rs : 0.f;
       sg += g[k][e];
-      sgx += g[k][e] * xh;
+      sgx = __builtin_fmaf(g[k][e], xh, sgx);
     }
     if (k < XL)
       ur[k < XL ? k : 0] = u4;
@@ -636,7 +660,7 @@ instnorm_bwd_greg_kernel(const float* __restrict__ dy, const float* __restrict__
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float xh = (u4[e] - mu) * rs;
-      o[e] = in ? kk * ((float)hw * g[k][e] - sg - xh * sgx) : 0.f;
+      o[e] = in ? in_du(kk, (float)hw, g[k][e], sg, xh, sgx) : 0.f;
       om = max(om, __float_as_uint(o[e]) & 0x7fffffffu);
     }
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -879,9 +903,14 @@ extern "C" int stx_instnorm_fwd(const float* x, const float* res, const float* g
   else if (hw % 4 == 0 && hw <= 4 * 1024 * 16)
     hipLaunchKernelGGL((instnorm_fwd_reg_kernel<1024, 16>), dim3(n * c), dim3(1024), 0, st, x,
                        res, gamma, beta, y, mean, rstd, c, hw, eps, relu, out_amax);
+  else if (hw >= 4 * 1024 * 4)  // big planes, as the backward: 16 waves per plane, and a
+                                // thread's serial fp32 chain a quarter as long (256 threads
+                                // add 257 terms each at 65 537 floats: past 2^-16 sum|u|)
+    hipLaunchKernelGGL(instnorm_fwd_kernel<1024>, dim3(n * c), dim3(1024), 0, st, x, res, gamma,
+                       beta, y, mean, rstd, c, hw, eps, relu, out_amax);
   else
-    hipLaunchKernelGGL(instnorm_fwd_kernel, dim3(n * c), dim3(NB), 0, st, x, res, gamma, beta, y,
-                       mean, rstd, c, hw, eps, relu, out_amax);
+    hipLaunchKernelGGL(instnorm_fwd_kernel<NB>, dim3(n * c), dim3(NB), 0, st, x, res, gamma, beta,
+                       y, mean, rstd, c, hw, eps, relu, out_amax);
   return check_launch("stx_instnorm_fwd");
 }
 
