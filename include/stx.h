@@ -790,6 +790,87 @@ int stx_image_condition(const void* src, const stx_image_meta* meta, int b, int 
                         const int* coef, int size, const float* mean, const float* std_,
                         float* out, void* tmp, size_t tmp_bytes, void* stream);
 
+/* JPEG decode split between host and GPU: the host parses the markers and Huffman-decodes
+ * the scan into quantised DCT coefficients, the GPU dequantises, runs libjpeg's "islow"
+ * integer IDCT, upsamples the chroma ("fancy" triangle filter) and converts YCbCr to RGB,
+ * into the packed HxWx3 uint8 layout stx_image_condition reads.  The output bytes equal
+ * libjpeg's (and so Pillow's) exactly.
+ *
+ * The two host functions are plain C++ (no GPU is opened) and return an STX_JPEG_* status.
+ * Decoded here: SOF0 / SOF1 (sequential Huffman), 8 bits, one interleaved scan, 1 component
+ * or 3 (YCbCr) with 1x1 chroma and luma sampling 1x1, 2x1 or 2x2, restart intervals, any
+ * 8-bit DQT / DHT.  Everything else -- progressive, arithmetic, lossless, 4 components, an
+ * Adobe transform other than YCbCr, RGB component ids, 16-bit quantisation tables, other
+ * samplings, several scans, bytes that are no JPEG -- is STX_JPEG_UNSUPPORTED.  A stream
+ * that ends early, holds a bad Huffman code, a wrong or misplaced restart marker, a run
+ * past coefficient 63, an undefined table or no EOI after the scan is STX_JPEG_CORRUPT.
+ * Neither function reads past len or writes past coef_bytes.
+ *
+ * The info query fills a stx_jpeg_desc: size, components, sampling factors, the block grid
+ * of each component padded to whole MCUs (bw x bh blocks) and coef_bytes =
+ * sum_c bw[c] bh[c] 128.  The entropy decode writes the coefficients as int16 in natural
+ * (row-major, de-zigzagged) order, component after component, each in block-raster order
+ * over its padded grid, and one uint16[64] quantisation table per component (natural
+ * order) to qtab [ncomp][64]; coef_bytes below the need is STX_JPEG_BAD_ARGS. */
+#define STX_JPEG_OK 0
+#define STX_JPEG_UNSUPPORTED 1
+#define STX_JPEG_CORRUPT 2
+#define STX_JPEG_BAD_ARGS 3
+typedef struct {
+  int status;              /* the STX_JPEG_* status the query returned */
+  int h, w, ncomp;
+  int hs[3], vs[3];        /* sampling factors (a lone component reports 1x1) */
+  int bw[3], bh[3];        /* blocks per row / per column of the padded grid */
+  int restart_interval;    /* MCUs between restart markers, 0: none */
+  long long coef_bytes;
+} stx_jpeg_desc;
+int stx_jpeg_info(const void* data, size_t len, stx_jpeg_desc* info);
+int stx_jpeg_entropy_decode(const void* data, size_t len, short* coef, size_t coef_bytes,
+                            unsigned short* qtab);
+
+/* The device stage for a batch.  jobs is a HOST array (read during the call, passed to the
+ * kernels by value); coef_base, rgb_base and tmp are device buffers, 16-byte aligned.
+ * Per job: a raw one copies h w 3 bytes from coef_base + coef_offset to rgb_base +
+ * rgb_offset.  Otherwise (a) every 8x8 block is dequantised, inverse-transformed (columns
+ * first, CONST_BITS 13, PASS1_BITS 2, descale by 11 then 18 with round-half-up) and written
+ * as clamp(v + 128, 0, 255) to the component's plane in tmp ((8 bh) rows of (8 bw) bytes,
+ * component after component from tmp_offset), then (b) each of the h x w pixels takes Y and
+ * the chroma upsampled from planes cut to ceil(w / hmax) x ceil(h / vmax):
+ *   2x1: even = (3 c + left + 1) >> 2, odd = (3 c + right + 2) >> 2, the first and last
+ *        output of a row the sample itself;
+ *   2x2: s = 3 c + the vertically nearer neighbour row (edge rows replicated), even =
+ *        (3 s + s_left + 8) >> 4, odd = (3 s + s_right + 7) >> 4, first column (4 s + 8) >> 4,
+ *        last (4 s + 7) >> 4;
+ * and R = Y + ((91881 Cr' + 32768) >> 16), B = Y + ((116130 Cb' + 32768) >> 16),
+ * G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16), Cb' = Cb - 128, Cr' = Cr - 128, clamped
+ * to 0..255; one component writes Y three times.  int32 arithmetic that wraps: coefficients
+ * no conforming encoder produces give unspecified pixels, never a fault.
+ *
+ * Checked before any launch (STX_E_INVALID): sizes 1..65535, ncomp, the sampling, bw / bh
+ * equal to the padded grid of (h, w, hmax, vmax), offsets non-negative and 16-byte
+ * aligned, every job's planes inside tmp_bytes (STX_E_WORKSPACE).  The caller guarantees
+ * that the coefficient, table and pixel ranges lie inside coef_base and rgb_base.  Two
+ * launches per 32 jobs; no allocation, no synchronisation.
+ *
+ * The layout query gives (size, last-member offset) of stx_jpeg_desc and stx_jpeg_job, as
+ * stx_abi_layout does for the older structs. */
+typedef struct {
+  long long rgb_offset;    /* bytes: the h x w x 3 output in rgb_base */
+  long long coef_offset;   /* bytes: component 0's blocks in coef_base, the others follow
+                              (raw: the h w 3 pixels) */
+  long long qtab_offset;   /* bytes: ncomp uint16[64] tables in coef_base */
+  long long tmp_offset;    /* bytes: the component planes in tmp */
+  int h, w;
+  int ncomp;               /* 1 or 3 */
+  int raw;                 /* non-zero: copy pixels through */
+  int hmax, vmax;          /* luma sampling: 1x1, 2x1 or 2x2 */
+  int bw[3], bh[3];        /* the padded block grids */
+} stx_jpeg_job;
+#define STX_JPEG_CHUNK 32  /* jobs per launch */
+int stx_jpeg_decode_batch(const stx_jpeg_job* jobs, int njobs, const void* coef_base,
+                          void* rgb_base, void* tmp, size_t tmp_bytes, void* stream);
+int stx_jpeg_layout(long long* out, int n);
+
 /* fp32 separable resampling (scale control, Gatys et al. 2017 section 6: the pyramid levels
  * of a coarse-to-fine transfer): [nc][hi][wi] planes to [nc][ho][wo], antialiased, half-pixel
  * centres -- the semantics of torch.nn.functional.interpolate(mode = "bilinear" | "bicubic",

@@ -119,6 +119,21 @@ class WgradParams(C.Structure):
                 ("in_mode", i32), ("ho", i32), ("wo", i32), ("no_split", i32)]
 
 
+class JpegDesc(C.Structure):
+    """Mirror of `stx_jpeg_desc` (include/stx.h)."""
+    _fields_ = [("status", i32), ("h", i32), ("w", i32), ("ncomp", i32), ("hs", i32 * 3),
+                ("vs", i32 * 3), ("bw", i32 * 3), ("bh", i32 * 3), ("restart_interval", i32),
+                ("coef_bytes", i64)]
+
+
+class JpegJob(C.Structure):
+    """Mirror of `stx_jpeg_job` (include/stx.h)."""
+    _fields_ = [("rgb_offset", i64), ("coef_offset", i64), ("qtab_offset", i64),
+                ("tmp_offset", i64), ("h", i32), ("w", i32), ("ncomp", i32), ("raw", i32),
+                ("hmax", i32), ("vmax", i32), ("bw", i32 * 3), ("bh", i32 * 3)]
+
+
+STX_JPEG_CHUNK = 32  # jobs per launch of stx_jpeg_decode_batch (include/stx.h)
 STX_WGRAD_NONE, STX_WGRAD_F32, STX_WGRAD_F16, STX_WGRAD_F16S2, STX_WGRAD_FEW16 = range(5)
 STX_FIN_MAX = 8
 STX_GUIDE_MAX = 4  # regions of a guided Gram (include/stx.h)
@@ -199,6 +214,10 @@ SIGNATURES = {
     "stx_tv_loss": (i32, [vp, vp, vp, f32, vp, i32, i32, i32, i32, f32, vp, sz, vp]),
     "stx_resample_coeffs": (i32, [i32, i32, vp, vp, i32]),
     "stx_image_condition": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
+    "stx_jpeg_info": (i32, [vp, sz, C.POINTER(JpegDesc)]),
+    "stx_jpeg_entropy_decode": (i32, [vp, sz, vp, sz, vp]),
+    "stx_jpeg_decode_batch": (i32, [C.POINTER(JpegJob), i32, vp, vp, vp, sz, vp]),
+    "stx_jpeg_layout": (i32, [vp, i32]),
     "stx_resample_plan": (i32, [i32, i32, i32, vp, vp, vp, i32]),
     "stx_resample2d_ws": (sz, [i32, i32, i32, i32, i32]),
     "stx_resample2d": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32,

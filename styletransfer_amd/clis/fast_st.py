@@ -14,6 +14,21 @@ def fast_st():
     """Fast Style Transfer"""
 
 
+def _loaders(batch_size, synthetic, gpu_decode):
+    """static_train's `loaders`: None is its default (local COCO, PIL decode in workers)."""
+    if synthetic and gpu_decode:
+        raise click.UsageError("--gpu-decode applies to the COCO loader, not to --synthetic")
+    if synthetic:
+        return lambda shard: dataset.get_synthetic_loader(batch_size, n_train=synthetic,
+                                                          shard=shard)
+    if gpu_decode:
+        # static_train's own call, with the switch on
+        return lambda shard: dataset.get_coco_loader(test_split=0.10, test_limit=20,
+                                                     batch_size=batch_size, shard=shard,
+                                                     gpu_decode=True)
+    return None
+
+
 @fast_st.command()
 @click.argument("style-image-path")
 @click.option("-e", "--epochs", default=50, help="How many epochs the training will take")
@@ -24,7 +39,11 @@ def fast_st():
               help="The weight we will assign to the style loss during the optimization")
 @click.option("--synthetic", default=0, type=int,
               help="Train on N synthetic images instead of local COCO (no network here)")
-def train(style_image_path, epochs, batch_size, content_weight, style_weight, synthetic):
+@click.option("--gpu-decode", is_flag=True,
+              help="COCO loader: workers only Huffman-decode the JPEGs, the IDCT and colour "
+                   "conversion run on the GPU (same pixels)")
+def train(style_image_path, epochs, batch_size, content_weight, style_weight, synthetic,
+          gpu_decode):
     """Train the fast style transfer network (checkpoint per epoch in data/models/)."""
     from .. import distributed
     distributed.from_env()  # torchrun: one rank per GPU, bound before anything allocates
@@ -33,9 +52,7 @@ def train(style_image_path, epochs, batch_size, content_weight, style_weight, sy
     style_image = img_utils.image_loader(
         os.path.join(constants.PROJECT_ROOT_PATH, style_image_path))
     net = network.ImageTransformNet(style_image, batch_size)
-    loaders = ((lambda shard: dataset.get_synthetic_loader(batch_size, n_train=synthetic,
-                                                            shard=shard))
-               if synthetic else None)
+    loaders = _loaders(batch_size, synthetic, gpu_decode)
     net.static_train(style_name=style_name, epochs=epochs, style_weight=style_weight,
                      content_weight=content_weight, loaders=loaders)
 
@@ -51,8 +68,11 @@ def train(style_image_path, epochs, batch_size, content_weight, style_weight, sy
               help="The weight we will assign to the style loss during the optimization")
 @click.option("--synthetic", default=0, type=int,
               help="Train on N synthetic images instead of local COCO (no network here)")
+@click.option("--gpu-decode", is_flag=True,
+              help="COCO loader: workers only Huffman-decode the JPEGs, the IDCT and colour "
+                   "conversion run on the GPU (same pixels)")
 def train_multi(style_image_paths, name, epochs, batch_size, content_weight, style_weight,
-                synthetic):
+                synthetic, gpu_decode):
     """Train ONE network on several styles (conditional instance norm): checkpoints
     data/models/fast_mst_NAME_epoch*.pth and the style names in fast_mst_NAME.styles.json."""
     from .. import distributed
@@ -64,9 +84,7 @@ def train_multi(style_image_paths, name, epochs, batch_size, content_weight, sty
     styles = [img_utils.image_loader(os.path.join(constants.PROJECT_ROOT_PATH, p))
               for p in style_image_paths]
     net = network.MultiStyleTransformNet(styles, batch_size, style_names=names)
-    loaders = ((lambda shard: dataset.get_synthetic_loader(batch_size, n_train=synthetic,
-                                                            shard=shard))
-               if synthetic else None)
+    loaders = _loaders(batch_size, synthetic, gpu_decode)
     net.static_train(style_name=name, epochs=epochs, style_weight=style_weight,
                      content_weight=content_weight, loaders=loaders)
 

@@ -18,7 +18,7 @@ import torch
 from PIL import Image
 from torch.utils.data import DataLoader, Dataset
 
-from . import c_logging, constants, img_utils
+from . import c_logging, constants, img_utils, jpeg
 from . import weights as W
 
 LOGGER = c_logging.get_logger()
@@ -33,9 +33,15 @@ class CocoDataset(Dataset):
     (a corrupt image is replaced by a random other one, as the reference does).
     decode_only=True returns the decoded HxWx3 uint8 array instead of the
     conditioned tensor: the conditioning then runs on the GPU for the whole batch
-    (img_utils.ImageConditioner, bit-identical to the PIL path)."""
+    (img_utils.ImageConditioner, bit-identical to the PIL path).
+    decode="coefs" stops one stage earlier: the worker reads the file and only
+    entropy-decodes it (jpeg.try_entropy_decode -> JpegCoefs), the IDCT, upsampling and
+    colour conversion run on the GPU too (jpeg.JpegBatchDecoder, the same pixels).  A file
+    that decoder reports as unsupported or corrupt takes the PIL path above -- with the
+    reference's random replacement on an exception -- and rides along as a decoded array."""
 
-    def __init__(self, images=None, image_limit=None, path=None, decode_only=False):
+    def __init__(self, images=None, image_limit=None, path=None, decode_only=False,
+                 decode=None):
         path = path or os.path.join(constants.PROJECT_ROOT_PATH, IMAGE_FOLDER_PATH)
         if images is None:
             images = sorted(f for f in os.listdir(path)
@@ -43,17 +49,28 @@ class CocoDataset(Dataset):
         self.path = path
         self.images = images[:image_limit] if image_limit else images
         self.decode_only = decode_only
+        if decode not in (None, "coefs"):
+            raise ValueError(f'decode must be None or "coefs", got {decode!r}')
+        self.decode = decode
 
     def __len__(self):
         return len(self.images)
 
     def __getitem__(self, idx):
+        if self.decode == "coefs":
+            try:
+                with open(os.path.join(self.path, self.images[idx]), "rb") as f:
+                    status, coefs = jpeg.try_entropy_decode(f.read())
+                if status == jpeg.OK:
+                    return coefs
+            except OSError:
+                pass  # the PIL path below meets the same error and replaces the image
         try:
             img = Image.open(os.path.join(self.path, self.images[idx]))
             # (convert("RGB") of an RGB image is a full copy: the same pixels without it)
             if img.mode != "RGB":
                 img = img.convert("RGB")
-            if self.decode_only:
+            if self.decode_only or self.decode == "coefs":
                 return np.asarray(img, dtype=np.uint8)
             return img_utils.image_loader_transform(img).cpu()
         except Exception:  # noqa: BLE001  (reference behaviour, :186-197)
@@ -77,6 +94,14 @@ def _pack_collate(batch):
         o += a.nbytes
     shapes = torch.tensor([a.shape[:2] for a in arrs], dtype=torch.int32).reshape(-1, 2)
     return packed, shapes
+
+
+def _coef_collate(batch):
+    """Entropy-decoded images (JpegCoefs) and PIL-decoded fallbacks (HxWx3 uint8) -> one
+    packed uint8 tensor holding the per-image records, the coefficients, the quantisation
+    tables and the raw pixels (jpeg.pack): like _pack_collate, one shared-memory tensor
+    per batch."""
+    return jpeg.pack(list(batch))
 
 
 def usable_cpus():
@@ -112,24 +137,32 @@ class GpuConditionedLoader:
     the GPU as [B, 1, 3, S, S] -- the shape static_train squeezes
     (stransfer/network.py:688).  Pipelined: batch k+depth's upload (pinned -> device)
     and conditioning kernels run on a side stream while the consumer works on batch k;
-    the consumer's stream waits on the batch's event, never the host."""
+    the consumer's stream waits on the batch's event, never the host.
+    jpeg_decode=True: the DataLoader yields _coef_collate batches instead
+    (CocoDataset(decode="coefs")), and the side stream first turns the coefficients into
+    the same packed RGB bytes (stx_jpeg_decode_batch) before it conditions them."""
 
-    def __init__(self, loader, size=None, device=None, depth=2):
+    def __init__(self, loader, size=None, device=None, depth=2, jpeg_decode=False):
         self.loader = loader
         self.batch_sampler = getattr(loader, "batch_sampler", None)
         self.cond = img_utils.ImageConditioner(size, device)
         self.depth = max(1, int(depth))
+        self.jdec = jpeg.JpegBatchDecoder(self.cond.device) if jpeg_decode else None
 
     def __len__(self):
         return len(self.loader)
 
     def _submit(self, item, side):
-        packed, shapes = item
         cond, dev = self.cond, self.cond.device
-        metas, coef, max_rows, tmp_bytes, src_bytes = cond._plan(
-            [tuple(hw) for hw in shapes.tolist()])
-        B, S = shapes.shape[0], cond.size
-        if packed.numel() != src_bytes:
+        if self.jdec is not None:
+            packed = item
+            jobs, shapes, rgb_bytes, jtmp_bytes = jpeg.plan(jpeg.records(packed))
+        else:
+            packed, shapes = item
+            shapes = [tuple(hw) for hw in shapes.tolist()]
+        metas, coef, max_rows, tmp_bytes, src_bytes = cond._plan(shapes)
+        B, S = len(shapes), cond.size
+        if (rgb_bytes if self.jdec is not None else packed.numel()) != src_bytes:
             raise ValueError("packed batch size does not match its shapes")
         mb = bytes(metas)
         head = torch.empty(len(mb) + coef.nbytes, dtype=torch.uint8).pin_memory()
@@ -138,6 +171,10 @@ class GpuConditionedLoader:
         hv[len(mb):] = coef.view(np.uint8).reshape(-1)
         with torch.cuda.stream(side):
             src = packed.to(dev, non_blocking=True)
+            if self.jdec is not None:
+                dpacked, src = src, torch.empty(src_bytes, dtype=torch.uint8, device=dev)
+                jtmp = torch.empty(max(jtmp_bytes, 16), dtype=torch.uint8, device=dev)
+                self.jdec.launch(dpacked, jobs, B, src, jtmp)
             hd = head.to(dev, non_blocking=True)
             tmp = torch.empty(max(tmp_bytes, 16), dtype=torch.uint8, device=dev)
             out = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
@@ -187,14 +224,17 @@ def _train_loader(ds, batch_size, shard, shuffle=True, seed=0, num_workers=0, co
 
 
 def get_coco_loader(batch_size=4, test_split=0.10, test_limit=None, path=None, shard=None,
-                    gpu_conditioning=None, num_workers=None):
+                    gpu_conditioning=None, num_workers=None, gpu_decode=False):
     """(test_loader, train_loader) over local COCO images (stransfer/dataset.py:314-360).
     `batch_size` is the global batch; with a data-parallel `shard` each rank's train
     loader yields its batch_size/world slice of every global batch.  With
     gpu_conditioning (default: when a GPU is present) the workers only decode (and pack
     the batch), the upload and the crop/resize/normalisation run on the GPU on a side
     stream, pipelined with the consumer (identical output); num_workers defaults to
-    default_workers() there and to 0 (the reference's DataLoader) on the PIL path."""
+    default_workers() there and to 0 (the reference's DataLoader) on the PIL path.
+    gpu_decode (opt-in, needs gpu_conditioning): the workers only entropy-decode the JPEGs
+    and the IDCT / upsampling / colour conversion run on the GPU as well (jpeg.py; the
+    same batches, bit for bit)."""
     path = path or os.path.join(constants.PROJECT_ROOT_PATH, IMAGE_FOLDER_PATH)
     if not os.path.isdir(path) or not os.listdir(path):
         raise FileNotFoundError(
@@ -207,17 +247,22 @@ def get_coco_loader(batch_size=4, test_split=0.10, test_limit=None, path=None, s
         test_imgs = test_imgs[:test_limit]
     if gpu_conditioning is None:
         gpu_conditioning = constants.DEVICE.type == "cuda"
+    if gpu_decode and not gpu_conditioning:
+        raise ValueError("gpu_decode needs gpu_conditioning (a GPU): the decoded pixels stay on "
+                         "the device")
     if gpu_conditioning:
         nw = default_workers() if num_workers is None else num_workers
         pin = torch.cuda.is_available()
-        test = GpuConditionedLoader(DataLoader(CocoDataset(test_imgs, path=path, decode_only=True),
+        dskw = {"decode": "coefs"} if gpu_decode else {"decode_only": True}
+        collate = _coef_collate if gpu_decode else _pack_collate
+        test = GpuConditionedLoader(DataLoader(CocoDataset(test_imgs, path=path, **dskw),
                                                batch_size=batch_size, shuffle=False,
-                                               collate_fn=_pack_collate, num_workers=min(nw, 2),
-                                               pin_memory=pin))
+                                               collate_fn=collate, num_workers=min(nw, 2),
+                                               pin_memory=pin), jpeg_decode=gpu_decode)
         train = GpuConditionedLoader(_train_loader(
-            CocoDataset(train_imgs, path=path, decode_only=True), batch_size, shard,
-            num_workers=nw, collate=_pack_collate, pin_memory=pin,
-            prefetch_factor=4 if nw > 0 else None))
+            CocoDataset(train_imgs, path=path, **dskw), batch_size, shard,
+            num_workers=nw, collate=collate, pin_memory=pin,
+            prefetch_factor=4 if nw > 0 else None), jpeg_decode=gpu_decode)
         return test, train
     num_workers = num_workers or 0
     test = DataLoader(CocoDataset(test_imgs, path=path), batch_size=batch_size, shuffle=False,
