@@ -871,6 +871,78 @@ int stx_jpeg_decode_batch(const stx_jpeg_job* jobs, int njobs, const void* coef_
                           void* rgb_base, void* tmp, size_t tmp_bytes, void* stream);
 int stx_jpeg_layout(long long* out, int n);
 
+/* JPEG encode, the decode's mirror: the GPU converts RGB to YCbCr, downsamples the chroma,
+ * runs libjpeg's "islow" integer forward DCT and quantises; the host only Huffman-codes.
+ * The files equal what libjpeg (and so Pillow, optimize=False) writes, byte for byte.
+ *
+ * Host (plain C++, STX_JPEG_* status).  The quantisation tables of a quality: the Annex K
+ * tables scaled as libjpeg does (quality clamped to 1..100, scale = q < 50 ? 5000 / q :
+ * 200 - 2 q, entry = clamp((base scale + 50) / 100, 1, 255)) to qtab [2][64], natural order,
+ * luma then chroma.  The bound is an upper limit of the file size, 0 for arguments the
+ * encoder does not take.  The entropy encode writes a complete baseline JFIF file from
+ * coefficients in exactly the layout stx_jpeg_entropy_decode writes (int16, natural order,
+ * component after component, block raster over the MCU-padded grid) and qtab [ncomp][64]
+ * (tables 1 and 2 must be equal): SOI, APP0 JFIF 1.01 (units 0, density 1x1), one 8-bit DQT
+ * per table, SOF0 (ids 1 2 3, tq 0 1 1), DHT DC0 AC0 DC1 AC1 (the Annex K tables; one
+ * component: DQT 0, DC0, AC0 only), SOS, the interleaved scan without restart markers, the
+ * last byte padded with 1-bits, EOI.  ncomp 1, or 3 with luma sampling 1x1, 2x1 or 2x2.
+ * STX_JPEG_BAD_ARGS, *len = 0 and nothing written past cap when cap is below the need,
+ * coef_bytes below the grid, a DC difference outside +-2047, an AC value outside +-1023, a
+ * table entry outside 1..255 or an unsupported sampling. */
+int stx_jpeg_quant_tables(int quality, unsigned short* qtab);
+size_t stx_jpeg_encode_bound(int h, int w, int ncomp, int hmax, int vmax);
+int stx_jpeg_entropy_encode(const short* coef, size_t coef_bytes, int h, int w, int ncomp,
+                            int hmax, int vmax, const unsigned short* qtab, void* out,
+                            size_t cap, size_t* len);
+
+/* The device stage of the encode for a batch; the conventions are stx_jpeg_decode_batch's
+ * (host job array passed by value, STX_JPEG_CHUNK jobs per launch, everything checked
+ * before any launch, no allocation, no synchronisation).  src_base, coef_base and tmp are
+ * device buffers, 16-byte aligned.  A job's source is packed h x w x 3 (ncomp 1: h x w)
+ * uint8, or (fp32 non-zero, ncomp 3) planar float [3][h][w] normalised with mean / std_:
+ *   v = x * std_ + mean (two fp32 roundings, no fma) clamped to [0, 255],
+ *   byte = min((int)(v * 255.0f), 255)
+ * -- img_utils.to_pil's byte wherever v * 255 < 256; above that to_pil wraps through an
+ * out-of-range float -> uint8 cast and this saturates (the one deliberate difference).
+ * (a) Colour and downsampling, to planes in tmp ((8 bh) rows of (8 bw) bytes, component
+ * after component from tmp_offset):
+ *   Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16
+ *   Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16
+ * source columns past w - 1 replicate column w - 1 and source rows past h - 1 row h - 1
+ * inside a row group; chroma is downsampled 2x2 as (a00 + a01 + a10 + a11 + bias) >> 2 (bias
+ * 1 on even output columns, 2 on odd) or 2x1 as (a0 + a1 + bias) >> 1 (bias 0 / 1), and the
+ * downsampled rows past ceil(h / vmax) - 1 replicate that row.
+ * (b) One thread per 8x8 block of the padded grid.  A block inside the component's real
+ * extent (ceil(ceil(w hs / hmax) / 8) x ceil(ceil(h vs / vmax) / 8) blocks) runs jfdctint.c's
+ * islow on sample - 128 (rows first, CONST_BITS 13, PASS1_BITS 2, DESCALE(x, n) =
+ * (x + (1 << (n - 1))) >> n) and quantises a = (|c| + 4 q) / (8 q) with the sign restored.
+ * A dummy block (outside the real extent) has zero AC and the quantised DC of the previous
+ * block of its component in MCU order, formed from the sum of that block's samples.
+ * Coefficients go to coef_base + coef_offset in the layout the entropy encode reads; the
+ * two tables are read from coef_base + qtab_offset (uint16 [2][64], natural order).
+ *
+ * Checked before any launch (STX_E_INVALID): sizes 1..65535, ncomp, the sampling, fp32 only
+ * with 3 components, bw / bh equal to the padded grid, offsets non-negative and 16-byte
+ * aligned, the planes inside tmp_bytes (STX_E_WORKSPACE).  The caller guarantees the
+ * source, table and coefficient ranges.  Two launches per 32 jobs.
+ * The layout query gives (size, last-member offset) of stx_jpeg_enc_job. */
+typedef struct {
+  long long src_offset;    /* bytes: the source image in src_base */
+  long long coef_offset;   /* bytes: component 0's blocks in coef_base, the others follow */
+  long long qtab_offset;   /* bytes: uint16 [2][64] luma and chroma tables in coef_base */
+  long long tmp_offset;    /* bytes: the component planes in tmp */
+  int h, w;
+  int ncomp;               /* 1 or 3 */
+  int fp32;                /* non-zero: planar normalised float source */
+  int hmax, vmax;          /* luma sampling: 1x1, 2x1 or 2x2 */
+  int bw[3], bh[3];        /* the padded block grids */
+  float mean[3], std_[3];  /* fp32 source: per-channel de-normalisation */
+} stx_jpeg_enc_job;
+int stx_jpeg_encode_batch(const stx_jpeg_enc_job* jobs, int njobs, const void* src_base,
+                          void* coef_base, void* tmp, size_t tmp_bytes, void* stream);
+int stx_jpeg_enc_layout(long long* out, int n);
+
 /* fp32 separable resampling (scale control, Gatys et al. 2017 section 6: the pyramid levels
  * of a coarse-to-fine transfer): [nc][hi][wi] planes to [nc][ho][wo], antialiased, half-pixel
  * centres -- the semantics of torch.nn.functional.interpolate(mode = "bilinear" | "bicubic",

@@ -133,7 +133,15 @@ class JpegJob(C.Structure):
                 ("hmax", i32), ("vmax", i32), ("bw", i32 * 3), ("bh", i32 * 3)]
 
 
-STX_JPEG_CHUNK = 32  # jobs per launch of stx_jpeg_decode_batch (include/stx.h)
+class JpegEncJob(C.Structure):
+    """Mirror of `stx_jpeg_enc_job` (include/stx.h)."""
+    _fields_ = [("src_offset", i64), ("coef_offset", i64), ("qtab_offset", i64),
+                ("tmp_offset", i64), ("h", i32), ("w", i32), ("ncomp", i32), ("fp32", i32),
+                ("hmax", i32), ("vmax", i32), ("bw", i32 * 3), ("bh", i32 * 3),
+                ("mean", f32 * 3), ("std_", f32 * 3)]
+
+
+STX_JPEG_CHUNK = 32  # jobs per launch of stx_jpeg_{de,en}code_batch (include/stx.h)
 STX_WGRAD_NONE, STX_WGRAD_F32, STX_WGRAD_F16, STX_WGRAD_F16S2, STX_WGRAD_FEW16 = range(5)
 STX_FIN_MAX = 8
 STX_GUIDE_MAX = 4  # regions of a guided Gram (include/stx.h)
@@ -218,6 +226,12 @@ SIGNATURES = {
     "stx_jpeg_entropy_decode": (i32, [vp, sz, vp, sz, vp]),
     "stx_jpeg_decode_batch": (i32, [C.POINTER(JpegJob), i32, vp, vp, vp, sz, vp]),
     "stx_jpeg_layout": (i32, [vp, i32]),
+    "stx_jpeg_quant_tables": (i32, [i32, vp]),
+    "stx_jpeg_encode_bound": (sz, [i32, i32, i32, i32, i32]),
+    "stx_jpeg_entropy_encode": (i32, [vp, sz, i32, i32, i32, i32, i32, vp, vp, sz,
+                                      C.POINTER(sz)]),
+    "stx_jpeg_encode_batch": (i32, [C.POINTER(JpegEncJob), i32, vp, vp, vp, sz, vp]),
+    "stx_jpeg_enc_layout": (i32, [vp, i32]),
     "stx_resample_plan": (i32, [i32, i32, i32, vp, vp, vp, i32]),
     "stx_resample2d_ws": (sz, [i32, i32, i32, i32, i32]),
     "stx_resample2d": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32,

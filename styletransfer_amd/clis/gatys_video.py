@@ -68,10 +68,20 @@ def parse_long_term(ctx, param, value):
               help="Multipliers of the style weight per style tap, conv1_1 .. conv3_1")
 @click.option("-o", "--out-dir", default="results/gatys_video/",
               help="Where the stylised frames 0.png, 1.png, ... are written")
+@click.option("--video", "video_out", default=None, metavar="OUT.avi",
+              help="Write the stylised frames as one Motion-JPEG .avi (through the GPU JPEG "
+                   "encoder) instead of PNG frames in -o")
+@click.option("--fps", default=24.0, help="With --video: the frame rate stored in the file")
+@click.option("--quality", default=90, type=click.IntRange(1, 100),
+              help="With --video: the JPEG quality")
+@click.option("--subsampling", type=click.Choice(["444", "422", "420"]), default="420",
+              help="With --video: the chroma subsampling")
 def gatys_video(frames_path, style_image_path, flow, save_flows, long_term, steps, first_steps,
-                temporal_weight, content_weight, style_weight, optimizer, layer_weights, out_dir):
+                temporal_weight, content_weight, style_weight, optimizer, layer_weights, out_dir,
+                video_out, fps, quality, subsampling):
     """Gatys style transfer of a clip, consistent from frame to frame.
-    FRAMES_PATH: a directory of frames or a .npy array [T, H, W, 3] uint8."""
+    FRAMES_PATH: a directory of frames, a .npy array [T, H, W, 3] uint8 or a Motion-JPEG
+    .avi."""
     from .. import img_utils, network, video
     root = constants.PROJECT_ROOT_PATH
     if save_flows is not None and flow != "auto":
@@ -101,11 +111,25 @@ def gatys_video(frames_path, style_image_path, flow, save_flows, long_term, step
     style_image = img_utils.image_loader(os.path.join(root, style_image_path))
     net = network.StyleNetwork(style_image)
     out_dir = os.path.join(root, out_dir)
-    os.makedirs(out_dir, exist_ok=True)
+    sink = None
+    if video_out is not None:
+        video_out = os.path.join(root, video_out)
+        os.makedirs(os.path.dirname(video_out) or ".", exist_ok=True)
+        sink = video.MjpegSink(video_out, fps, quality, subsampling, constants.DEVICE)
+    else:
+        os.makedirs(out_dir, exist_ok=True)
     out = net.train_gatys_video(frames, style_image, flows, steps=steps, first_steps=first_steps,
                                 temporal_weight=temporal_weight, optimizer=optimizer,
                                 style_weight=style_weight, content_weight=content_weight,
                                 style_layer_weights=layer_weights, long_term=long_term)
-    for i, y in enumerate(out):
-        img_utils.imshow(y[0], path=os.path.join(out_dir, f"{i}.png"))
-    LOGGER.info("Done! %d stylised frames have been saved to: %s", len(frames), out_dir)
+    try:
+        for i, y in enumerate(out):
+            if sink is not None:
+                sink.write(y)
+            else:
+                img_utils.imshow(y[0], path=os.path.join(out_dir, f"{i}.png"))
+    finally:
+        if sink is not None:
+            sink.close()
+    LOGGER.info("Done! %d stylised frames have been saved to: %s", len(frames),
+                video_out if sink is not None else out_dir)

@@ -1,6 +1,6 @@
 """`video_st` commands (mirror of stransfer/clis/video_st.py:11-87).  Decoding
-video files needs imageio, which this image lacks; frame directories and .npy
-frame arrays work without it."""
+video files needs imageio, which this image lacks; frame directories, .npy frame
+arrays and Motion-JPEG .avi files work without it."""
 import click
 
 
@@ -57,13 +57,23 @@ def train(style_image_path, epochs, batch_size, content_weight, style_weight, te
 @click.option("--fps", default=24.0)
 @click.option("--preserve-color", is_flag=True,
               help="Keep each frame's colours: only the luminance of the result is used")
-def convert_video(video_path, style_name, out_dir, fps, preserve_color):
+@click.option("--format", "format_", type=click.Choice(["png", "mjpeg"]), default="png",
+              help="png = frames in workdir/ (the default); mjpeg = one Motion-JPEG .avi "
+                   "written through the GPU JPEG encoder")
+@click.option("--quality", default=90, type=click.IntRange(1, 100),
+              help="With --format mjpeg: the JPEG quality")
+@click.option("--subsampling", type=click.Choice(["444", "422", "420"]), default="420",
+              help="With --format mjpeg: the chroma subsampling")
+def convert_video(video_path, style_name, out_dir, fps, preserve_color, format_, quality,
+                  subsampling):
     """Convert a video with a pretrained video network (stransfer/clis/video_st.py).
-    VIDEO_PATH: a video file (needs imageio), a directory of frames or a .npy array."""
+    VIDEO_PATH: a Motion-JPEG .avi, another video file (needs imageio), a directory of
+    frames or a .npy array."""
     import torch
 
     from .. import network
     sty = network.VideoTransformNet(torch.rand([3, 255, 255]))  # as the reference CLI
     out = sty.process_video(video_path=video_path, style_name=style_name, out_dir=out_dir,
-                            fps=fps, preserve_color=preserve_color)
+                            fps=fps, preserve_color=preserve_color, format=format_,
+                            quality=quality, subsampling=subsampling)
     click.echo(f"stylised video: {out}")

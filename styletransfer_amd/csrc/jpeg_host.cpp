@@ -11,6 +11,9 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+#if defined(__SSE2__)
+#include <emmintrin.h>
+#endif
 
 #include "../../include/stx.h"
 
@@ -349,6 +352,295 @@ extern "C" int stx_jpeg_layout(long long* out, int n) {
   const long long v[] = {(long long)sizeof(stx_jpeg_desc),
                          (long long)offsetof(stx_jpeg_desc, coef_bytes),
                          (long long)sizeof(stx_jpeg_job), (long long)offsetof(stx_jpeg_job, bh)};
+  const int m = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; out && i < n && i < m; ++i) out[i] = v[i];
+  return m;
+}
+
+// ------------------------------------------------------------------------ the encoder
+namespace {
+
+// ITU T.81 Annex K.1: the example quantisation tables (natural order)
+const uint8_t K_LUMA[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,
+                            14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+                            18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                            49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+const uint8_t K_CHROMA[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99,
+                              24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                              99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                              99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+
+// Annex K.3: the typical Huffman tables, as (counts of lengths 1..16, symbols)
+struct StdHuff {
+  uint8_t counts[16];
+  int nsyms;
+  const uint8_t* syms;
+};
+const uint8_t DC_SYMS[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t AC0_SYMS[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07,
+    0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0,
+    0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28,
+    0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49,
+    0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
+    0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89,
+    0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7,
+    0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5,
+    0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+    0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8,
+    0xf9, 0xfa};
+const uint8_t AC1_SYMS[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71,
+    0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0,
+    0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26,
+    0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68,
+    0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87,
+    0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5,
+    0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+    0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8,
+    0xf9, 0xfa};
+// [class * 2 + id]: DC0, DC1, AC0, AC1
+const StdHuff STD_HUFF[4] = {
+    {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, DC_SYMS},
+    {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, DC_SYMS},
+    {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, 162, AC0_SYMS},
+    {{0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}, 162, AC1_SYMS}};
+
+// symbol -> (code, length); length 0: the table has no such symbol
+struct EncHuff {
+  uint16_t code[256];
+  uint8_t len[256];
+};
+struct EncTables {
+  EncHuff h[4];
+  uint8_t zpos[64];  // natural index -> zigzag index
+  EncTables() {
+    memset(h, 0, sizeof(h));
+    for (int i = 0; i < 64; ++i) zpos[ZIGZAG[i]] = (uint8_t)i;
+    for (int t = 0; t < 4; ++t) {
+      uint32_t code = 0;
+      int k = 0;
+      for (int l = 1; l <= 16; ++l) {
+        for (int i = 0; i < STD_HUFF[t].counts[l - 1]; ++i, ++k, ++code) {
+          h[t].code[STD_HUFF[t].syms[k]] = (uint16_t)code;
+          h[t].len[STD_HUFF[t].syms[k]] = (uint8_t)l;
+        }
+        code <<= 1;
+      }
+    }
+  }
+};
+const EncTables ENC;
+
+constexpr size_t ENC_HEADER_MAX = 1024;     // all markers of a 3-component file: 623 bytes
+constexpr size_t ENC_BLOCK_MAX = 2 * 212;   // 20 DC + 63 * 26 AC bits, every byte stuffed
+
+bool enc_sampling_ok(int h, int w, int ncomp, int hmax, int vmax) {
+  if (h < 1 || h > 65535 || w < 1 || w > 65535) return false;
+  if (ncomp == 1) return hmax == 1 && vmax == 1;
+  if (ncomp != 3) return false;
+  return (hmax == 1 && vmax == 1) || (hmax == 2 && vmax == 1) || (hmax == 2 && vmax == 2);
+}
+
+// MSB-first bit writer bounded by cap: a byte that does not fit is dropped and `ok` cleared
+struct BitOut {
+  uint8_t* p;
+  size_t cap, pos = 0;
+  uint64_t acc = 0;
+  int n = 0;
+  bool ok = true;
+  BitOut(uint8_t* p_, size_t cap_) : p(p_), cap(cap_) {}
+  inline void byte(uint8_t b) {
+    if (pos < cap) p[pos++] = b; else ok = false;
+  }
+  inline void bytes(const void* s, size_t k) {
+    if (k <= cap - pos) { memcpy(p + pos, s, k); pos += k; } else ok = false;
+  }
+  inline void be16(int v) { byte((uint8_t)(v >> 8)); byte((uint8_t)v); }
+  inline void drain() {  // whole bytes out, FF followed by 00
+    if (n >= 32 && cap - pos >= 4) {  // four bytes at once when none of them is FF
+      const uint32_t v = (uint32_t)(acc >> (n - 32)), x = ~v;
+      if (!((x - 0x01010101u) & ~x & 0x80808080u)) {
+        const uint32_t be = __builtin_bswap32(v);
+        memcpy(p + pos, &be, 4);
+        pos += 4;
+        n -= 32;
+      }
+    }
+    while (n >= 8) {
+      const uint8_t b = (uint8_t)(acc >> (n - 8));
+      n -= 8;
+      byte(b);
+      if (b == 0xFF) byte(0);
+    }
+  }
+  inline void put(uint32_t code, int len) {  // len <= 32, at most 31 bits pending
+    acc = (acc << len) | code;
+    n += len;
+    if (n >= 32) drain();
+  }
+  inline void finish() {  // pad the last byte with 1-bits
+    if (n & 7) put((1u << (8 - (n & 7))) - 1u, 8 - (n & 7));
+    drain();
+  }
+};
+
+inline int bit_size(uint32_t a) { return a ? 32 - __builtin_clz(a) : 0; }
+
+// bit i set: b[i] != 0 (natural order)
+inline uint64_t nonzero_mask(const int16_t* b) {
+  uint64_t m = 0;
+#if defined(__SSE2__)
+  const __m128i z = _mm_setzero_si128();
+  for (int r = 0; r < 4; ++r) {
+    const __m128i lo = _mm_cmpeq_epi16(_mm_loadu_si128((const __m128i*)(b + 16 * r)), z);
+    const __m128i hi = _mm_cmpeq_epi16(_mm_loadu_si128((const __m128i*)(b + 16 * r + 8)), z);
+    m |= (uint64_t)(uint16_t)~_mm_movemask_epi8(_mm_packs_epi16(lo, hi)) << (16 * r);
+  }
+#else
+  for (int i = 0; i < 64; ++i) m |= (uint64_t)(b[i] != 0) << i;
+#endif
+  return m;
+}
+
+}  // namespace
+
+extern "C" int stx_jpeg_quant_tables(int quality, unsigned short* qtab) {
+  if (!qtab) return STX_JPEG_BAD_ARGS;
+  const int q = quality < 1 ? 1 : (quality > 100 ? 100 : quality);
+  const int scale = q < 50 ? 5000 / q : 200 - 2 * q;
+  for (int t = 0; t < 2; ++t)
+    for (int i = 0; i < 64; ++i) {
+      const int v = ((t ? K_CHROMA : K_LUMA)[i] * scale + 50) / 100;
+      qtab[64 * t + i] = (unsigned short)(v < 1 ? 1 : (v > 255 ? 255 : v));
+    }
+  return STX_JPEG_OK;
+}
+
+extern "C" size_t stx_jpeg_encode_bound(int h, int w, int ncomp, int hmax, int vmax) {
+  if (!enc_sampling_ok(h, w, ncomp, hmax, vmax)) return 0;
+  const size_t mx = ((size_t)w + 8 * hmax - 1) / (8 * hmax);
+  const size_t my = ((size_t)h + 8 * vmax - 1) / (8 * vmax);
+  const size_t blocks = mx * my * (size_t)(ncomp == 1 ? 1 : hmax * vmax + 2);
+  return ENC_HEADER_MAX + blocks * ENC_BLOCK_MAX;
+}
+
+extern "C" int stx_jpeg_entropy_encode(const short* coef, size_t coef_bytes, int h, int w,
+                                       int ncomp, int hmax, int vmax,
+                                       const unsigned short* qtab, void* out, size_t cap,
+                                       size_t* len) {
+  if (len) *len = 0;
+  if (!coef || !qtab || !len || (!out && cap) || !enc_sampling_ok(h, w, ncomp, hmax, vmax))
+    return STX_JPEG_BAD_ARGS;
+  const int mcux = (w + 8 * hmax - 1) / (8 * hmax), mcuy = (h + 8 * vmax - 1) / (8 * vmax);
+  int hs[3] = {hmax, 1, 1}, vs[3] = {vmax, 1, 1}, bw[3];
+  const int16_t* base[3];
+  size_t need = 0;
+  for (int c = 0; c < ncomp; ++c) {
+    bw[c] = mcux * hs[c];
+    base[c] = (const int16_t*)coef + need / 2;
+    need += (size_t)bw[c] * ((size_t)mcuy * vs[c]) * 128;
+  }
+  if (coef_bytes < need) return STX_JPEG_BAD_ARGS;
+  for (int t = 0; t < ncomp; ++t)
+    for (int i = 0; i < 64; ++i)
+      if (qtab[64 * t + i] < 1 || qtab[64 * t + i] > 255) return STX_JPEG_BAD_ARGS;
+  if (ncomp == 3 && memcmp(qtab + 64, qtab + 128, 128) != 0) return STX_JPEG_BAD_ARGS;
+
+  BitOut o((uint8_t*)out, cap);
+  static const uint8_t APP0[] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0,
+                                 1,    1,    0,    0,    1, 0,  1,   0,   0};
+  o.bytes(APP0, sizeof(APP0));
+  const int ntab = ncomp == 1 ? 1 : 2;
+  for (int t = 0; t < ntab; ++t) {
+    const uint8_t hd[] = {0xFF, 0xDB, 0, 67, (uint8_t)t};
+    o.bytes(hd, sizeof(hd));
+    for (int i = 0; i < 64; ++i) o.byte((uint8_t)qtab[64 * t + ZIGZAG[i]]);
+  }
+  {
+    const uint8_t hd[] = {0xFF, 0xC0, 0, (uint8_t)(8 + 3 * ncomp), 8};
+    o.bytes(hd, sizeof(hd));
+    o.be16(h);
+    o.be16(w);
+    o.byte((uint8_t)ncomp);
+    for (int c = 0; c < ncomp; ++c) {
+      o.byte((uint8_t)(c + 1));
+      o.byte((uint8_t)((hs[c] << 4) | vs[c]));
+      o.byte((uint8_t)(c ? 1 : 0));
+    }
+  }
+  for (int id = 0; id < ntab; ++id)
+    for (int cls = 0; cls < 2; ++cls) {  // DC0, AC0, DC1, AC1
+      const StdHuff& s = STD_HUFF[cls * 2 + id];
+      const uint8_t hd[] = {0xFF, 0xC4, 0, (uint8_t)(19 + s.nsyms), (uint8_t)((cls << 4) | id)};
+      o.bytes(hd, sizeof(hd));
+      o.bytes(s.counts, 16);
+      o.bytes(s.syms, (size_t)s.nsyms);
+    }
+  {
+    const uint8_t hd[] = {0xFF, 0xDA, 0, (uint8_t)(6 + 2 * ncomp), (uint8_t)ncomp};
+    o.bytes(hd, sizeof(hd));
+    for (int c = 0; c < ncomp; ++c) {
+      o.byte((uint8_t)(c + 1));
+      o.byte((uint8_t)(c ? 0x11 : 0x00));
+    }
+    const uint8_t tl[] = {0, 63, 0};
+    o.bytes(tl, sizeof(tl));
+  }
+  if (!o.ok) return STX_JPEG_BAD_ARGS;
+
+  int pred[3] = {0, 0, 0};
+  for (int my = 0; my < mcuy; ++my) {
+    for (int mx = 0; mx < mcux; ++mx) {
+      for (int c = 0; c < ncomp; ++c) {
+        const EncHuff& dc = ENC.h[c ? 1 : 0];
+        const EncHuff& ac = ENC.h[c ? 3 : 2];
+        for (int by = 0; by < vs[c]; ++by)
+          for (int bx = 0; bx < hs[c]; ++bx) {
+            const int16_t* blk =
+                base[c] + ((size_t)(my * vs[c] + by) * bw[c] + (size_t)(mx * hs[c] + bx)) * 64;
+            const int diff = (int)blk[0] - pred[c];
+            pred[c] = blk[0];
+            if (diff < -2047 || diff > 2047) return STX_JPEG_BAD_ARGS;
+            int s = bit_size((uint32_t)(diff < 0 ? -diff : diff));  // <= 11
+            o.put(dc.code[s], dc.len[s]);
+            if (s) o.put((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1u), s);
+            // the non-zero AC coefficients as a bit mask in zigzag order: only they are visited
+            uint64_t zz = 0;
+            for (uint64_t m = nonzero_mask(blk) & ~1ull; m; m &= m - 1)
+              zz |= 1ull << ENC.zpos[__builtin_ctzll(m)];
+            int prev = 0;
+            for (; zz; zz &= zz - 1) {
+              const int k = __builtin_ctzll(zz);
+              int run = k - prev - 1;
+              prev = k;
+              const int v = blk[ZIGZAG[k]];
+              if (v < -1023 || v > 1023) return STX_JPEG_BAD_ARGS;
+              for (; run > 15; run -= 16) o.put(ac.code[0xF0], ac.len[0xF0]);
+              s = bit_size((uint32_t)(v < 0 ? -v : v));  // 1..10
+              const int sym = (run << 4) | s;
+              o.put(ac.code[sym], ac.len[sym]);
+              o.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1u), s);
+            }
+            if (prev != 63) o.put(ac.code[0], ac.len[0]);
+            if (!o.ok) return STX_JPEG_BAD_ARGS;
+          }
+      }
+    }
+  }
+  o.finish();
+  o.byte(0xFF);
+  o.byte(0xD9);
+  if (!o.ok) return STX_JPEG_BAD_ARGS;
+  *len = o.pos;
+  return STX_JPEG_OK;
+}
+
+extern "C" int stx_jpeg_enc_layout(long long* out, int n) {
+  const long long v[] = {(long long)sizeof(stx_jpeg_enc_job),
+                         (long long)offsetof(stx_jpeg_enc_job, std_)};
   const int m = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; out && i < n && i < m; ++i) out[i] = v[i];
   return m;

@@ -854,16 +854,20 @@ class VideoTransformNet(ImageTransformNet):
             self.has_external_weights = False
 
     def process_video(self, video_path: str, style_name="nsp", working_dir="workdir/",
-                      out_dir="results/", fps=24.0, preserve_color=False):
+                      out_dir="results/", fps=24.0, preserve_color=False, format="png",
+                      quality=90, subsampling="4:2:0"):
         """stransfer/network.py:1071-1158 on the graph-captured per-frame engine
         (styletransfer_amd/video.py); frames come from imageio when installed, or from
-        a directory of frames / a .npy frame array.  preserve_color: every output frame
-        keeps its input frame's colours (the luminance merge inside the frame graph)."""
+        a directory of frames / a .npy frame array / a Motion-JPEG .avi.  preserve_color:
+        every output frame keeps its input frame's colours (the luminance merge inside the
+        frame graph).  format "mjpeg": one MJPEG .avi written through the GPU JPEG encoder
+        (quality, subsampling) instead of PNG frames."""
         from . import video
         self.load_state_dict(_load_latest_model_weigths(model_name="video_st",
                                                         style_name=style_name))
         return video.process_video(self, video_path, style_name, working_dir, out_dir, fps,
-                                   preserve_color=preserve_color)
+                                   preserve_color=preserve_color, format=format,
+                                   quality=quality, subsampling=subsampling)
 
     def get_temporal_loss(self, old_content, old_stylized, current_content, current_stylized,
                           temporal_weight=1) -> torch.Tensor:

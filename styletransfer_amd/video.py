@@ -33,6 +33,19 @@ VIDEO_EXTS = (".mp4", ".avi", ".mov", ".mkv", ".gif", ".webm")
 FRAME_EXTS = (".png", ".jpg", ".jpeg", ".bmp")
 
 
+def mjpeg_avi(source):
+    """video_io.read_mjpeg_avi(source) if source names an .avi file it accepts (Motion-JPEG:
+    read without a codec library), else None (other video files go through imageio)."""
+    if not (isinstance(source, str) and source.lower().endswith(".avi")
+            and os.path.isfile(source)):
+        return None
+    from . import video_io
+    try:
+        return video_io.read_mjpeg_avi(source)
+    except ValueError:
+        return None
+
+
 def iterate_raw_frames(source, max_frames=90 * 24) -> Iterator[np.ndarray]:
     """Decoded frames of a video as HxWx3 uint8 arrays (the sources of iterate_frames)."""
     from PIL import Image
@@ -47,6 +60,10 @@ def iterate_raw_frames(source, max_frames=90 * 24) -> Iterator[np.ndarray]:
             return (int(digits) if digits else -1, name)
         names = sorted((n for n in os.listdir(source) if n.lower().endswith(FRAME_EXTS)), key=key)
         frames = (np.asarray(Image.open(os.path.join(source, n)).convert("RGB")) for n in names)
+    elif mjpeg_avi(source) is not None:
+        import io
+        frames = (np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))
+                  for b in mjpeg_avi(source)[3])
     elif isinstance(source, str) and source.lower().endswith(VIDEO_EXTS):
         try:
             import imageio
@@ -183,33 +200,127 @@ class FrameEngine:
         return float(self.scal[0]) * temporal_weight
 
 
+class MjpegSink:
+    """Stylised frames [1, 3, h, w] (normalised fp32, on the GPU) -> an MJPEG AVI file: the
+    JPEG encoder's fp32 front end reads the frame where it lies, the int16 coefficients cross
+    to the host and are Huffman-coded on the encoder's background thread while the GPU works
+    on the next frame; no fp32 copy to the host, no PNG."""
+
+    def __init__(self, path, fps=24.0, quality=90, subsampling="4:2:0", device=None):
+        from . import jpeg
+        if subsampling not in jpeg.SAMPLINGS:
+            raise ValueError(f"subsampling {subsampling!r}: 4:4:4, 4:2:2 or 4:2:0")
+        self.path, self.fps = path, fps
+        self.quality, self.subsampling = int(quality), subsampling
+        self.enc = jpeg.JpegBatchEncoder(device)
+        self.writer = None
+        self.inflight = 0
+        self.frames = 0
+
+    def _drain(self, keep):
+        while self.inflight > keep:
+            for data in self.enc.collect():
+                self.writer.write(data)
+            self.inflight -= 1
+
+    def write(self, y: torch.Tensor):
+        if self.writer is None:
+            from . import video_io
+            self.writer = video_io.MjpegAviWriter(self.path, self.fps, y.shape[-2], y.shape[-1])
+        # (the encoder has read y when submit returns control of the stream: the kernels are
+        # enqueued before the engine's next replay overwrites the static output)
+        self.enc.submit([y], self.quality, self.subsampling)
+        self.inflight += 1
+        self.frames += 1
+        self._drain(1)
+
+    def close(self):
+        try:
+            if self.writer is not None:
+                self._drain(0)
+        finally:
+            self.enc.close()
+            if self.writer is not None:
+                self.writer.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def iterate_device_frames(source, device=None, max_frames=90 * 24):
+    """The frames of an MJPEG .avi as uint8 [h, w, 3] DEVICE tensors: Huffman-decoded on the
+    host, the pixel stages on the GPU (jpeg.JpegBatchDecoder: Pillow's pixels); a frame the
+    host decoder does not take is decoded by PIL and rides along as raw pixels."""
+    from . import jpeg
+    avi = mjpeg_avi(source)
+    if avi is None:
+        raise ValueError(f"{source!r}: not a Motion-JPEG .avi file")
+    dec = jpeg.JpegBatchDecoder(device)
+    for i, data in enumerate(avi[3]):
+        if i >= max_frames:
+            break
+        rgb, shapes = dec.decode([data])
+        yield rgb.view(shapes[0][0], shapes[0][1], 3)
+
+
 def process_video(net, video_path, style_name="nsp", working_dir="workdir/", out_dir="results/",
-                  fps=24.0, graph=True, max_frames=90 * 24, preserve_color=False) -> str:
+                  fps=24.0, graph=True, max_frames=90 * 24, preserve_color=False,
+                  format="png", quality=90, subsampling="4:2:0") -> str:
     """VideoTransformNet.process_video (stransfer/network.py:1071-1158) on FrameEngine.
-    preserve_color: every written frame keeps its input frame's colours."""
+    preserve_color: every written frame keeps its input frame's colours.
+
+    format "png" (the default): frames 0.png, 1.png, ... in working_dir, muxed to an .mp4 when
+    imageio is installed.  format "mjpeg": the frames go from the engine's output through the
+    GPU JPEG encoder (quality, subsampling) into out_dir/video_st_<style>.avi (MjpegSink); no
+    PNG, no frames in working_dir; returns that path.  A Motion-JPEG .avi as video_path is
+    read without imageio, and decoded on the GPU when the engine runs on one."""
+    if format not in ("png", "mjpeg"):
+        raise ValueError(f"format {format!r}: 'png' or 'mjpeg'")
+    mjpeg = format == "mjpeg"
     working_dir = os.path.join(constants.PROJECT_ROOT_PATH, working_dir)
     out_dir = os.path.join(constants.PROJECT_ROOT_PATH, out_dir)
-    import shutil
-    shutil.rmtree(working_dir, ignore_errors=True)
-    os.makedirs(working_dir, exist_ok=True)
+    if not mjpeg:
+        import shutil
+        shutil.rmtree(working_dir, ignore_errors=True)
+        os.makedirs(working_dir, exist_ok=True)
     os.makedirs(out_dir, exist_ok=True)
     eng = None
     S = constants.IMSIZE
-    for i, frame in enumerate(iterate_raw_frames(video_path, max_frames)):
-        # decoded uint8 frames go to the GPU as they are; crop, resize and normalisation
-        # run inside the per-frame graph (bit-identical to image_loader_transform)
-        if eng is None or eng.cond.h != frame.shape[0] or eng.cond.w != frame.shape[1]:
-            if eng is not None:  # a clip whose frame size changes: a new engine, as the
-                prev = eng.prev.clone()  # reference, but keep the recurrence going
-            eng2 = FrameEngine(net, (1, 3, S, S), constants.DEVICE, graph=graph,
-                               raw_hw=frame.shape[:2], preserve_color=preserve_color)
-            if eng is not None:
-                eng2.prev.copy_(prev)
-                eng2.prev_frame.copy_(eng.prev_frame)
-                eng2.started = True
-            eng = eng2
-        y = eng.step_raw(frame)
-        img_utils.imshow(y[0], path=os.path.join(working_dir, f"{i}.png"))
+    sink = None
+    if mjpeg:
+        sink = MjpegSink(os.path.join(out_dir, f"video_st_{style_name}.avi"), fps, quality,
+                         subsampling, constants.DEVICE)
+    if mjpeg_avi(video_path) is not None and torch.device(constants.DEVICE).type == "cuda":
+        frames = iterate_device_frames(video_path, constants.DEVICE, max_frames)
+    else:
+        frames = iterate_raw_frames(video_path, max_frames)
+    try:
+        for i, frame in enumerate(frames):
+            # decoded uint8 frames go to the GPU as they are; crop, resize and normalisation
+            # run inside the per-frame graph (bit-identical to image_loader_transform)
+            if eng is None or eng.cond.h != frame.shape[0] or eng.cond.w != frame.shape[1]:
+                if eng is not None:  # a clip whose frame size changes: a new engine, as the
+                    prev = eng.prev.clone()  # reference, but keep the recurrence going
+                eng2 = FrameEngine(net, (1, 3, S, S), constants.DEVICE, graph=graph,
+                                   raw_hw=tuple(frame.shape[:2]), preserve_color=preserve_color)
+                if eng is not None:
+                    eng2.prev.copy_(prev)
+                    eng2.prev_frame.copy_(eng.prev_frame)
+                    eng2.started = True
+                eng = eng2
+            y = eng.step_raw(frame)
+            if mjpeg:
+                sink.write(y)
+            else:
+                img_utils.imshow(y[0], path=os.path.join(working_dir, f"{i}.png"))
+    finally:
+        if sink is not None:
+            sink.close()
+    if mjpeg:
+        return sink.path
     final = os.path.join(out_dir, f"video_st_{style_name}.mp4")
     try:
         import imageio
