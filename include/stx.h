@@ -358,6 +358,22 @@ typedef struct stx_loss_parts {
 } stx_loss_parts;
 int stx_loss_finalize(const stx_loss_parts* lp, float* losses, const float* extra, int m,
                       const float* w_host, float* total, void* stream);
+/* stx_conv_weight_compose16 (above) with up to two rider blocks beside the compose grid,
+ * each doing what would otherwise be a one-block launch of its own in a Gatys iteration's
+ * serial chain (the slab and out_amax are the bits of stx_conv_weight_compose16):
+ *   lp != NULL:       stx_loss_finalize(lp, losses, extra, m, w_host, total) -- the same
+ *                     values; the loss partials must be complete in stream order (the Gram
+ *                     finalize ran before this call);
+ *   step_dev != NULL: the first half of stx_adam_step_clear: ++*step_dev and the step's
+ *                     bias-corrected scalars into adam_ws (stx_adam_ws() bytes), nothing
+ *                     cleared; stx_adam_step_prepared then applies the update.
+ * Either rider may be absent.  No block waits on another. */
+int stx_conv_weight_compose16_tail(const float* A, int pitch, const float* a_amax, const float* w,
+                                   const float* w_amax, int cout, int cin, const float* scale,
+                                   void* wtT16, float* out_amax, const stx_loss_parts* lp,
+                                   float* losses, const float* extra, int m, const float* w_host,
+                                   float* total, int* step_dev, void* adam_ws, float lr,
+                                   float beta1, float beta2, void* stream);
 /* dz (+)= s * A[b]·z[b] (+ aux_scale*aux) — Gram backward as a 1x1 MFMA conv with
  * per-image weights; z viewed [b][c][h][w]; s = *acc_scale_dev (or 1 if NULL) */
 int stx_gram_bwd(const float* coef, const float* z, float* dz, int b, int c, int h, int w,
@@ -580,6 +596,12 @@ int stx_adam_step(float* p, const float* g, float* m, float* v, long long n, flo
 int stx_adam_step_clear(float* p, const float* g, float* m, float* v, long long n, float lr,
                         float beta1, float beta2, float eps, int* step_dev, void* ws,
                         float* clear, int clear_n, void* stream);
+/* the second half alone: the update with the scalars a prepare rider
+ * (stx_conv_weight_compose16_tail) left in ws for this step, in one launch that also zeroes
+ * clear[0 .. clear_n).  p, m and v end as stx_adam_step_clear leaves them. */
+int stx_adam_step_prepared(float* p, const float* g, float* m, float* v, long long n, float beta1,
+                           float beta2, float eps, const void* ws, float* clear, int clear_n,
+                           void* stream);
 
 /* InstanceNorm2d(affine) forward, per (n,c) plane over hw (biased var, eps):
  *   u = x (+ res);  y = (u-mean)*rstd*gamma + beta, formed as fma(u, gsc, sh) with

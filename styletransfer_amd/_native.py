@@ -164,6 +164,9 @@ SIGNATURES = {
     "stx_conv_weight16up_bytes": (sz, [i32, i32]),
     "stx_conv_weight_prep16_up": (i32, [vp, vp, vp, i32, i32, vp]),
     "stx_conv_weight_compose16": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    "stx_conv_weight_compose16_tail": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp,
+                                             C.POINTER(LossParts), vp, vp, i32,
+                                             C.POINTER(f32), vp, vp, vp, f32, f32, f32, vp]),
     "stx_amax": (i32, [vp, i64, vp, vp]),
     "stx_conv_weight_prep_batch": (i32, [C.POINTER(WprepJob), i32, vp]),
     "stx_conv2d_wgrad_plan": (i32, [C.POINTER(WgradParams), C.POINTER(sz)]),
@@ -209,6 +212,7 @@ SIGNATURES = {
     "stx_adam_ws": (sz, []),
     "stx_adam_step": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, vp, vp, vp]),
     "stx_adam_step_clear": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
+    "stx_adam_step_prepared": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, vp, vp, i32, vp]),
     "stx_instnorm_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp]),
     "stx_instnorm_bwd_ws": (sz, [i32, i32]),
     "stx_instnorm_param_grads": (i32, [C.POINTER(PGradJob), i32, vp]),

@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "conv_epi.h"
+#include "tail.h"
 #include "wprep.h"
 #include "../../include/stx.h"
 
@@ -1713,23 +1714,22 @@ __global__ void __launch_bounds__(256) weight_prep_batch_kernel(WprepJobs b) {
 // order (fixed order), splits and stores 8-B runs of the slab.
 constexpr int WC_R = 16, WC_K = 64;
 
-__global__ void __launch_bounds__(256)
-weight_compose16_kernel(const float* __restrict__ A, int pitch, const float* __restrict__ a_amax,
-                        const float* __restrict__ W, const float* __restrict__ w_amax, int C,
-                        int cin, const float* __restrict__ scale, _Float16* __restrict__ slab,
-                        float* __restrict__ out_amax) {
+// block (bx, by) of the grid (ceil(K / 64), ceil(C / 16)); la: the A^T tile (C <= 256); lw:
+// W columns k0 .. k0 + 63 and, after the sums, the three wave partials (80 KB per block in
+// all: two blocks per CU)
+__device__ __forceinline__ void weight_compose16_body(
+    const float* __restrict__ A, int pitch, const float* __restrict__ a_amax,
+    const float* __restrict__ W, const float* __restrict__ w_amax, int C, int cin,
+    const float* __restrict__ scale, _Float16* __restrict__ slab, float* __restrict__ out_amax,
+    int bx, int by, float (*la)[WC_R], float (*lw)[WC_K]) {
   typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
   const int K = cin * 9;
-  __shared__ __attribute__((aligned(16))) float la[256][WC_R];  // A^T tile (C <= 256)
-  // W columns k0 .. k0 + 63; after the sums, the three wave partials (80 KB per block in
-  // all: two blocks per CU)
-  __shared__ __attribute__((aligned(16))) float lw[256][WC_K];
   float (*red)[WC_R * WC_K] = reinterpret_cast<float (*)[WC_R * WC_K]>(&lw[0][0]);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c0 = blockIdx.y * WC_R, k0 = blockIdx.x * WC_K;
+  const int c0 = by * WC_R, k0 = bx * WC_K;
   const float sc = scale ? *scale : 1.f;
   const float bound = fabsf(sc) * (float)C * read_amax(a_amax) * read_amax(w_amax);
-  if (blockIdx.x == 0 && blockIdx.y == 0 && tid < STX_AMAX_SLOTS) out_amax[tid] = bound;
+  if (bx == 0 && by == 0 && tid < STX_AMAX_SLOTS) out_amax[tid] = bound;
   const float sw = __builtin_ldexpf(1.f, 15 - amax_exp(bound));
   {
     // A rows c0 .. c0 + 15 (-> la, transposed) and the block's W columns [C][64] (-> lw):
@@ -1806,6 +1806,58 @@ weight_compose16_kernel(const float* __restrict__ A, int pitch, const float* __r
     *reinterpret_cast<f16x4*>(slab + u0 * 8 + e0) = hi;
     *reinterpret_cast<f16x4*>(slab + u1 * 8 + e0) = lo;
   }
+}
+
+__global__ void __launch_bounds__(256)
+weight_compose16_kernel(const float* __restrict__ A, int pitch, const float* __restrict__ a_amax,
+                        const float* __restrict__ W, const float* __restrict__ w_amax, int C,
+                        int cin, const float* __restrict__ scale, _Float16* __restrict__ slab,
+                        float* __restrict__ out_amax) {
+  __shared__ __attribute__((aligned(16))) float la[256][WC_R];
+  __shared__ __attribute__((aligned(16))) float lw[256][WC_K];
+  weight_compose16_body(A, pitch, a_amax, W, w_amax, C, cin, scale, slab, out_amax, blockIdx.x,
+                        blockIdx.y, la, lw);
+}
+
+// The compose launch with riders (stx_conv_weight_compose16_tail): blocks [0, nblk) are the
+// compose grid in its own order (block L = (L % nbx, L / nbx)); up to two more blocks each
+// run a one-block kernel of the iteration that would otherwise be a launch of its own in
+// the serial chain -- the loss finalize (its partials are complete: the Gram finalize ran
+// before this launch) and Adam's step counter and bias corrections (they depend on nothing
+// but the previous step).  A rider block branches here, before any barrier of the compose
+// body, all of its threads alike; no block waits on another.  A rider's few floats of LDS
+// alias the compose tile: a buffer of its own would cost the second block per CU.
+struct ComposeTail {
+  stx_loss_parts lp;    // loss rider (losses == nullptr: absent), loss_finalize_kernel's
+  float* losses;        // arguments
+  const float* extra;
+  float* total;
+  LossWF w;
+  int m;
+  int nblk, nbx;        // compose blocks, and per row
+  int* step;            // prepare rider (step == nullptr: absent), adam_prepare_kernel's
+  AdamScalars* sc;      // arguments
+  double lr, b1, b2;
+};
+
+__global__ void __launch_bounds__(256)
+weight_compose16_tail_kernel(const float* __restrict__ A, int pitch,
+                             const float* __restrict__ a_amax, const float* __restrict__ W,
+                             const float* __restrict__ w_amax, int C, int cin,
+                             const float* __restrict__ scale, _Float16* __restrict__ slab,
+                             float* __restrict__ out_amax, ComposeTail t) {
+  __shared__ __attribute__((aligned(16))) float la[256][WC_R];
+  __shared__ __attribute__((aligned(16))) float lw[256][WC_K];
+  const int L = blockIdx.x;
+  if (L >= t.nblk) {
+    if (t.losses && L == t.nblk)
+      loss_finalize_body<4>(t.lp, t.losses, t.extra, t.m, t.w, t.total, &la[0][0]);
+    else if (threadIdx.x == 0)
+      adam_prepare_body(t.step, t.sc, t.lr, t.b1, t.b2);
+    return;
+  }
+  weight_compose16_body(A, pitch, a_amax, W, w_amax, C, cin, scale, slab, out_amax, L % t.nbx,
+                        L / t.nbx, la, lw);
 }
 
 // stx_conv_params.unpool_out (validated by stx_conv2d): 32 x 4 tiles of d, 64 couts
@@ -2016,6 +2068,59 @@ extern "C" int stx_conv_weight_compose16(const float* A, int pitch, const float*
                      0, st, A, pitch, a_amax, w, w_amax, cout, cin, scale,
                      reinterpret_cast<_Float16*>(wtT16), out_amax);
   return check_launch("stx_conv_weight_compose16");
+}
+
+extern "C" int stx_conv_weight_compose16_tail(
+    const float* A, int pitch, const float* a_amax, const float* w, const float* w_amax, int cout,
+    int cin, const float* scale, void* wtT16, float* out_amax, const stx_loss_parts* lp,
+    float* losses, const float* extra, int m, const float* w_host, float* total, int* step_dev,
+    void* adam_ws, float lr, float beta1, float beta2, void* stream) {
+  if (!A || !a_amax || !w || !w_amax || !wtT16 || !out_amax || cout <= 0 || cout > 256 ||
+      cin <= 0 || cin % 4 || pitch < cout || (reinterpret_cast<uintptr_t>(w) & 15)) {
+    set_error("stx_conv_weight_compose16_tail: invalid arguments (1 <= cout <= 256, "
+              "cin % 4 == 0, w 16-byte aligned)");
+    return STX_E_INVALID;
+  }
+  const long long total_h = (long long)rup(cout, 16) * 9 * 2 * rup(cin, 64);
+  if ((long long)cout * cin * 9 >= (1ll << 31) || total_h >= (1ll << 31)) {
+    set_error("stx_conv_weight_compose16_tail: weight too large");
+    return STX_E_INVALID;
+  }
+  if (lp && (lp->k < 0 || lp->k > 8 || m < 0 || lp->k + m > 16 || !losses || (m && !extra) ||
+             (total && !w_host))) {  // (stx_loss_finalize's conditions)
+    set_error("stx_conv_weight_compose16_tail: invalid loss rider");
+    return STX_E_INVALID;
+  }
+  if (step_dev && !adam_ws) {
+    set_error("stx_conv_weight_compose16_tail: the prepare rider needs adam_ws");
+    return STX_E_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (cout % 16 || cin % 64)
+    (void)hipMemsetAsync(wtT16, 0, (size_t)total_h * sizeof(_Float16), st);
+  ComposeTail t{};
+  t.nbx = cdiv(cin * 9, WC_K);
+  t.nblk = t.nbx * cdiv(cout, WC_R);
+  if (lp) {
+    t.lp = *lp;
+    t.losses = losses;
+    t.extra = extra;
+    t.total = total;
+    t.m = m;
+    for (int i = 0; i < lp->k + m && w_host; ++i) t.w.w[i] = w_host[i];
+  }
+  if (step_dev) {
+    t.step = step_dev;
+    t.sc = (AdamScalars*)adam_ws;
+    t.lr = (double)lr;
+    t.b1 = (double)beta1;
+    t.b2 = (double)beta2;
+  }
+  const int riders = (lp ? 1 : 0) + (step_dev ? 1 : 0);
+  hipLaunchKernelGGL(weight_compose16_tail_kernel, dim3(t.nblk + riders), dim3(256), 0, st, A,
+                     pitch, a_amax, w, w_amax, cout, cin, scale,
+                     reinterpret_cast<_Float16*>(wtT16), out_amax, t);
+  return check_launch("stx_conv_weight_compose16_tail");
 }
 
 extern "C" int stx_conv_weight_prep16(const float* w, void* wt16, float* w_amax, int cout, int cin,

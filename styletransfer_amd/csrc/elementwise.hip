@@ -3,6 +3,7 @@
 // two-stage with a fixed block count and a fixed summation order, so results
 // are bit-reproducible run to run (no float atomics).
 #include "common.h"
+#include "tail.h"
 #include "../../include/stx.h"
 
 namespace stx {
@@ -239,10 +240,7 @@ __global__ void relu_bwd_kernel(const float* __restrict__ dy, const float* __res
 // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2); denom = sqrt(v)/sqrt(bc2) + eps;
 // p.addcdiv_(m, denom, -lr/bc1).  Step counter lives on the device so a captured
 // graph replays correctly; scalars computed in fp64 like torch's Python floats.
-struct AdamScalars {
-  float step_size;   // lr / bc1
-  float bc2_sqrt;    // sqrt(1 - b2^t)
-};
+// (AdamScalars and the step-counter body: tail.h, shared with the compose launch's rider)
 
 // thread 0: the step counter and bias corrections; all threads: zero `clear` (the
 // caller's per-iteration amax groups, stx_adam_step_clear) -- one launch fewer per
@@ -251,17 +249,16 @@ __global__ void adam_prepare_kernel(int* step, AdamScalars* sc, double lr, doubl
                                     float* clear, int clear_n) {
   for (int i = threadIdx.x; i < clear_n; i += blockDim.x) clear[i] = 0.f;
   if (threadIdx.x) return;
-  const int t = ++(*step);
-  const double bc1 = 1.0 - pow(b1, (double)t);
-  const double bc2 = 1.0 - pow(b2, (double)t);
-  sc->step_size = (float)(lr / bc1);
-  sc->bc2_sqrt = (float)sqrt(bc2);
+  adam_prepare_body(step, sc, lr, b1, b2);
 }
 
+// clear (stx_adam_step_prepared; clear_n = 0 otherwise): zeroed by the last block once its
+// elements are done -- nothing runs beside this launch, and it does not read `clear`
 __global__ void __launch_bounds__(256)
 adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
             float* __restrict__ v, long long n, float b1, float b2, float eps,
-            const AdamScalars* __restrict__ sc, int vec) {
+            const AdamScalars* __restrict__ sc, int vec, float* __restrict__ clear,
+            int clear_n) {
   const float step_size = sc->step_size, bc2s = sc->bc2_sqrt;
   const float w1 = 1.f - b1, w2 = 1.f - b2;
   const long long n4 = vec ? n / 4 : 0;
@@ -292,6 +289,8 @@ adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restric
     const float denom = sqrtf(vv) / bc2s + eps;
     p[i] = p[i] + (-step_size * mm) / denom;
   }
+  if (blockIdx.x == gridDim.x - 1)
+    for (int i = threadIdx.x; i < clear_n; i += blockDim.x) clear[i] = 0.f;
 }
 
 // ------------------------------------------------------------------ upsample
@@ -578,8 +577,23 @@ extern "C" int stx_adam_step_clear(float* p, const float* g, float* m, float* v,
   const long long units = vec ? n / 4 : n;
   const int blocks = (int)std::max<long long>(1, std::min<long long>((units + 255) / 256, 4096));
   hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, n, beta1, beta2,
-                     eps, sc, vec);
+                     eps, sc, vec, (float*)nullptr, 0);
   return check_launch("stx_adam_step");
+}
+
+extern "C" int stx_adam_step_prepared(float* p, const float* g, float* m, float* v, long long n,
+                                      float beta1, float beta2, float eps, const void* ws,
+                                      float* clear, int clear_n, void* stream) {
+  if (n <= 0 || !p || !g || !m || !v || !ws || clear_n < 0 || (clear_n > 0 && !clear)) {
+    set_error("stx_adam_step_prepared: invalid args");
+    return STX_E_INVALID;
+  }
+  const int vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
+  const long long units = vec ? n / 4 : n;
+  const int blocks = (int)std::max<long long>(1, std::min<long long>((units + 255) / 256, 4096));
+  hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                     beta1, beta2, eps, (const AdamScalars*)ws, vec, clear, clear_n);
+  return check_launch("stx_adam_step_prepared");
 }
 
 extern "C" int stx_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr,

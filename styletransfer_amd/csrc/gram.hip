@@ -15,7 +15,10 @@
 // scales, mirrors, and for the style loss also forms (G-T), the per-tile squared
 // sum, and the backward coefficient matrix A = cA*(G-T) + alpha*I used by the
 // Gram backward dF = A F (a 1x1 MFMA conv, see stx_gram_bwd).
+#include <type_traits>
+
 #include "common.h"
+#include "tail.h"
 #include "../../include/stx.h"
 
 namespace stx {
@@ -763,7 +766,13 @@ __host__ __device__ inline int fin_groups(int nsplit) { return nsplit <= 8 ? 4 :
 __host__ __device__ inline int fin_blocks_per_tile(int nsplit) { return FSUB / fin_groups(nsplit); }
 
 // block (bx, by) of a finalize over grid (ntu * fin_blocks_per_tile(nsplit), b)
-template <int G>
+// DEEP: a split-lane with more than one round of partials (nsplit > 4 * KL: the 64-channel
+// taps at 512^2 walk 8 rounds, the launch lasts as long as those blocks do) issues four
+// rounds (16 float4 loads), then two, before it waits, where the plain loop has one round
+// (4 loads) per memory round trip.  Every accumulator takes the same addends in the same
+// order either way: the same bits.  (G > 1 means nsplit <= 16, at most one partial per
+// split-lane: no chain.)
+template <int G, bool DEEP>
 __device__ __forceinline__ void gram_finalize_body_g(
     const float* __restrict__ ws, int c, int nsplit, float scale, float* __restrict__ g_out,
     const float* __restrict__ target, long long t_bstride, float* __restrict__ coef, int cpad,
@@ -783,6 +792,30 @@ __device__ __forceinline__ void gram_finalize_body_g(
     const f32x4* p4 = reinterpret_cast<const f32x4*>(src) + q4;
     constexpr int ST = GT * GT / 4;  // float4s per partial
     int k = kl;
+    // R rounds: 4 R loads issued together, then added round by round (s0 .. s3 in turn)
+    auto rounds = [&](auto rc) {
+      constexpr int R = decltype(rc)::value;
+      f32x4 a[4 * R];
+#pragma unroll
+      for (int j = 0; j < 4 * R; ++j) a[j] = p4[(size_t)(k + j * KL) * ST];
+      // (left to itself the scheduler sinks most of 16 loads between the adds to save
+      // registers, and the first add waits on vmcnt(0) after a single load)
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        s0 += a[4 * j + 0];
+        s1 += a[4 * j + 1];
+        s2 += a[4 * j + 2];
+        s3 += a[4 * j + 3];
+      }
+    };
+    if constexpr (DEEP && G == 1) {
+      for (; k + 15 * KL < nsplit; k += 16 * KL) rounds(std::integral_constant<int, 4>{});
+      if (k + 7 * KL < nsplit) {
+        rounds(std::integral_constant<int, 2>{});
+        k += 8 * KL;
+      }
+    }
     for (; k + 3 * KL < nsplit; k += 4 * KL) {
       const f32x4 a0 = p4[(size_t)(k + 0 * KL) * ST], a1 = p4[(size_t)(k + 1 * KL) * ST];
       const f32x4 a2 = p4[(size_t)(k + 2 * KL) * ST], a3 = p4[(size_t)(k + 3 * KL) * ST];
@@ -839,6 +872,7 @@ __device__ __forceinline__ void gram_finalize_body_g(
 
 // one block of the finalize `q` describes (stx_gram_fin_job: the one description of a
 // finalize, immediate or batched)
+template <bool DEEP>
 __device__ __forceinline__ void gram_finalize_body(const stx_gram_fin_job& q, int bx, int by) {
   __shared__ float part[FKL * (FEL + 1)];
   __shared__ float red[FNT / 64];
@@ -860,7 +894,7 @@ __device__ __forceinline__ void gram_finalize_body(const stx_gram_fin_job& q, in
     }
   }
 #define STX_FIN_BODY(G)                                                                      \
-  gram_finalize_body_g<G>(q.parts, q.c, q.nsplit, q.scale, q.g_out, q.target, q.t_bstride,   \
+  gram_finalize_body_g<G, DEEP>(q.parts, q.c, q.nsplit, q.scale, q.g_out, q.target, q.t_bstride,   \
                           q.coef, q.cpad, q.cA, q.alpha, q.loss_parts, bx, by, part,         \
                           q.coef_amax)
   switch (fin_groups(q.nsplit)) {
@@ -872,8 +906,19 @@ __device__ __forceinline__ void gram_finalize_body(const stx_gram_fin_job& q, in
 }
 
 // grid (ntu * fin_blocks_per_tile(nsplit), b)
+template <bool DEEP>
 __global__ void __launch_bounds__(FNT) gram_finalize_kernel(stx_gram_fin_job q) {
-  gram_finalize_body(q, blockIdx.x, blockIdx.y);
+  gram_finalize_body<DEEP>(q, blockIdx.x, blockIdx.y);
+}
+
+// The deep loop's 16 loads cost registers (92 VGPRs against 52: two blocks per CU instead of
+// four), which pays only where a chain reaches four rounds: a launch takes the DEEP kernel
+// when one of its jobs does, else the plain one (fast_st's batch-8 taps have two rounds at
+// most and keep the kernel and the occupancy they had).  Either kernel gives the same bits.
+// (STX_FIN_DEEP=0: always the plain kernel, A/B; read at every launch so that one process
+// can capture both.)
+static bool fin_deep(int nsplit) {
+  return nsplit >= 16 * FKL && STX_KNOB("STX_FIN_DEEP", 1) != 0;
 }
 
 // the finalizes of several style losses (one per VGG tap) in ONE launch: block ranges
@@ -884,29 +929,14 @@ struct FinBatch {
   int njobs;
 };
 
+template <bool DEEP>
 __global__ void __launch_bounds__(FNT) gram_finalize_batch_kernel(FinBatch fb) {
   int j = 0;
   while (j + 1 < fb.njobs && (int)blockIdx.x >= fb.blk0[j + 1]) ++j;
   const stx_gram_fin_job& q = fb.job[j];
   const int local = blockIdx.x - fb.blk0[j];
   const int nt = cdiv(q.c, GT), nbx = nt * (nt + 1) / 2 * fin_blocks_per_tile(q.nsplit);
-  gram_finalize_body(q, local % nbx, local / nbx);
-}
-
-// one wave: the fixed-order sum of n loss partials (4 lane-strided accumulators, then a
-// wave tree) -- shared by sum_parts_kernel and loss_finalize_kernel so the deferred and
-// direct style losses are the same bits
-__device__ __forceinline__ float wave_sum_parts(const float* __restrict__ parts, int n, int lane) {
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int i = lane;
-  for (; i + 192 < n; i += 256) {
-    s0 += parts[i];
-    s1 += parts[i + 64];
-    s2 += parts[i + 128];
-    s3 += parts[i + 192];
-  }
-  for (; i < n; i += 64) s0 += parts[i];
-  return wave_sum((s0 + s1) + (s2 + s3));
+  gram_finalize_body<DEEP>(q, local % nbx, local / nbx);
 }
 
 // single wave: loss = inv * sum(parts)
@@ -921,10 +951,6 @@ __global__ void zero_kernel(float* p, long long n) {
        i += (long long)gridDim.x * blockDim.x)
     p[i] = 0.f;
 }
-
-struct LossWF {
-  float w[16];
-};
 
 static void gram_geometry(int c, int hw, int b, int& nsplit, int& split_len, int& ntu) {
   const int nt = cdiv(c, GT);
@@ -1053,8 +1079,11 @@ static void gram_finalize(const stx_gram_fin_job& q, stx_gram_fin_job* defer, fl
     return;
   }
   const int nt = cdiv(q.c, GT), ntu = nt * (nt + 1) / 2;
-  hipLaunchKernelGGL(gram_finalize_kernel, dim3(ntu * fin_blocks_per_tile(q.nsplit), q.b),
-                     dim3(FNT), 0, st, q);
+  const dim3 grid(ntu * fin_blocks_per_tile(q.nsplit), q.b);
+  if (fin_deep(q.nsplit))
+    hipLaunchKernelGGL(gram_finalize_kernel<true>, grid, dim3(FNT), 0, st, q);
+  else
+    hipLaunchKernelGGL(gram_finalize_kernel<false>, grid, dim3(FNT), 0, st, q);
   if (q.target && loss)
     hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(64), 0, st, q.loss_parts,
                        q.b * ntu * FSUB, (float)(1.0 / ((double)q.b * q.c * q.c)), loss);
@@ -1071,30 +1100,15 @@ extern "C" size_t stx_style_loss_parts(int b, int c, int hw, int* nparts) {
 }
 
 namespace stx {
-// one block: losses[i] = inv_i * sum(parts_i) (wave i, the order of sum_parts_kernel, so
-// the values are identical), then the weighted total
+// one block: losses[i] = inv_i * sum(parts_i) (wave i), then the weighted total
+// (loss_finalize_body, tail.h)
 __global__ void __launch_bounds__(512) loss_finalize_kernel(stx_loss_parts lp,
                                                            float* __restrict__ losses,
                                                            const float* __restrict__ extra,
                                                            int m, LossWF w,
                                                            float* __restrict__ total) {
-  // wave i reduces loss i (the sum_parts_kernel order), all losses in parallel
   __shared__ float lv[8];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (wave < lp.k) {
-    const float s = wave_sum_parts(lp.parts[wave], lp.nparts[wave], lane);
-    if (lane == 0) lv[wave] = s * lp.inv[wave];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int i = 0; i < lp.k; ++i) {
-      losses[i] = lv[i];
-      t += w.w[i] * lv[i];
-    }
-    for (int j = 0; j < m; ++j) t += w.w[lp.k + j] * extra[j];
-    if (total) *total = t;
-  }
+  loss_finalize_body<8>(lp, losses, extra, m, w, total, lv);
 }
 }  // namespace stx
 
@@ -1230,7 +1244,7 @@ extern "C" int stx_gram_finalize_batch(const stx_gram_fin_job* jobs, int njobs, 
     return STX_E_INVALID;
   }
   FinBatch fb{};
-  int blocks = 0;
+  int blocks = 0, longest = 0;
   for (int j = 0; j < njobs; ++j) {
     const stx_gram_fin_job& q = jobs[j];
     if (!q.parts || q.c <= 0 || q.nsplit <= 0 || q.b <= 0 || !q.loss_parts) {
@@ -1240,12 +1254,17 @@ extern "C" int stx_gram_finalize_batch(const stx_gram_fin_job* jobs, int njobs, 
     const int nt = cdiv(q.c, GT);
     fb.job[j] = q;
     fb.blk0[j] = blocks;
+    longest = std::max(longest, q.nsplit);
     blocks += nt * (nt + 1) / 2 * fin_blocks_per_tile(q.nsplit) * q.b;
   }
   fb.blk0[njobs] = blocks;
   fb.njobs = njobs;
-  hipLaunchKernelGGL(gram_finalize_batch_kernel, dim3(blocks), dim3(FNT), 0, (hipStream_t)stream,
-                     fb);
+  if (fin_deep(longest))
+    hipLaunchKernelGGL(gram_finalize_batch_kernel<true>, dim3(blocks), dim3(FNT), 0,
+                       (hipStream_t)stream, fb);
+  else
+    hipLaunchKernelGGL(gram_finalize_batch_kernel<false>, dim3(blocks), dim3(FNT), 0,
+                       (hipStream_t)stream, fb);
   return check_launch("stx_gram_finalize_batch");
 }
 

@@ -337,12 +337,16 @@ def conv_weight_prep16_up(w: torch.Tensor):
 
 
 def conv_weight_compose16(coef, coef_amax, w: torch.Tensor, w_amax, out_amax, scale=None,
-                          out=None):
+                          out=None, loss_job=None, adam_prepare=None):
     """The data-gradient split slab of w' = scale * A w (A = coef [cout][pitch], one image's
     Gram-backward operator, coef_amax >= max|A|; w [cout][cin][3][3], w_amax >= max|w|):
     conv^T_w(A z) = conv^T_{w'}(z) (stx_conv_weight_compose16, one launch).  out_amax (an
     amax group) receives the slab's scale bound; the conv takes wt16=(slab, out_amax).
-    out: the slab buffer to reuse.  Returns the slab."""
+    out: the slab buffer to reuse.  Returns the slab.
+
+    loss_job (a LossFinalizeJob) / adam_prepare (an AdamPrepare): run as rider blocks of
+    this launch instead of as one-block launches of their own
+    (stx_conv_weight_compose16_tail); both are marked done."""
     _req(w, "weight")
     _req(coef, "coef")
     cout, cin, ks, _ = w.shape
@@ -351,10 +355,26 @@ def conv_weight_compose16(coef, coef_amax, w: torch.Tensor, w_amax, out_amax, sc
     if out is None:
         out = torch.empty(L.stx_conv_weight16_bytes(cin, cout, ks, 1), device=w.device,
                           dtype=torch.uint8)
-    check(L.stx_conv_weight_compose16(coef.data_ptr(), coef.shape[-1], coef_amax.data_ptr(),
-                                      w.data_ptr(), w_amax.data_ptr(), cout, cin, _p(scale),
-                                      out.data_ptr(), out_amax.data_ptr(), _stream()),
-          "stx_conv_weight_compose16")
+    if loss_job is None and adam_prepare is None:
+        check(L.stx_conv_weight_compose16(coef.data_ptr(), coef.shape[-1], coef_amax.data_ptr(),
+                                          w.data_ptr(), w_amax.data_ptr(), cout, cin, _p(scale),
+                                          out.data_ptr(), out_amax.data_ptr(), _stream()),
+              "stx_conv_weight_compose16")
+        return out
+    j, a = loss_job, adam_prepare
+    check(L.stx_conv_weight_compose16_tail(
+        coef.data_ptr(), coef.shape[-1], coef_amax.data_ptr(), w.data_ptr(), w_amax.data_ptr(),
+        cout, cin, _p(scale), out.data_ptr(), out_amax.data_ptr(),
+        C.byref(j.lp) if j else None, j.losses.data_ptr() if j else None,
+        _p(j.extra) if j else None, j.m if j else 0, j.w if j else None,
+        _p(j.total) if j else None,
+        a.step_dev.data_ptr() if a else None, a.ws.data_ptr() if a else None,
+        a.lr if a else 0.0, a.beta1 if a else 0.0, a.beta2 if a else 0.0, _stream()),
+        "stx_conv_weight_compose16_tail")
+    if j:
+        j.done = True
+    if a:
+        a.done = True
     return out
 
 
@@ -852,21 +872,37 @@ def style_loss_from_parts(gparts, nparts, b, c, hw, target, weight=1.0, diag_alp
                        parts=gparts, nparts=nparts, mse_parts=mse_parts, mse_out=mse_out)
 
 
+class LossFinalizeJob:
+    """One stx_loss_finalize call, described: launch() runs it as a launch of its own;
+    conv_weight_compose16(loss_job=...) runs it as a rider of the compose launch.  Either
+    way once (done)."""
+
+    def __init__(self, parts, losses, extra=None, weights=None, total=None):
+        self.lp = N.LossParts()
+        assert len(parts) <= 8
+        for i, (ptr, n, inv) in enumerate(parts):
+            self.lp.parts[i], self.lp.nparts[i], self.lp.inv[i] = ptr, n, inv
+        self.lp.k = len(parts)
+        self.losses, self.extra, self.total = losses, extra, total
+        self.m = 0 if extra is None else extra.numel()
+        self.w = None
+        if weights is not None:
+            self.w = (C.c_float * len(weights))(*[float(x) for x in weights])
+        self.done = False
+
+    def launch(self):
+        if not self.done:
+            check(lib().stx_loss_finalize(C.byref(self.lp), self.losses.data_ptr(),
+                                          _p(self.extra), self.m, self.w, _p(self.total),
+                                          _stream()), "stx_loss_finalize")
+            self.done = True
+        return self.losses
+
+
 def loss_finalize(parts, losses, extra=None, weights=None, total=None):
     """One launch: losses[i] = reduced deferred style-loss partials (parts from
     style_loss(defer_ws=...)), and optionally total = sum w_i losses_i + sum w extra."""
-    lp = N.LossParts()
-    assert len(parts) <= 8
-    for i, (ptr, n, inv) in enumerate(parts):
-        lp.parts[i], lp.nparts[i], lp.inv[i] = ptr, n, inv
-    lp.k = len(parts)
-    m = 0 if extra is None else extra.numel()
-    w = None
-    if weights is not None:
-        w = (C.c_float * len(weights))(*[float(x) for x in weights])
-    check(lib().stx_loss_finalize(C.byref(lp), losses.data_ptr(), _p(extra), m, w, _p(total),
-                                  _stream()), "stx_loss_finalize")
-    return losses
+    return LossFinalizeJob(parts, losses, extra, weights, total).launch()
 
 
 def gram_bwd_fused(coef, z, out=None, acc_scale=None, up_dp=None, aux=None, aux_scale=0.0,
@@ -1056,6 +1092,29 @@ def adam_step(p, g, m, v, step_dev, ws, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-
     check(lib().stx_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
                               float(lr), float(beta1), float(beta2), float(eps),
                               step_dev.data_ptr(), ws.data_ptr(), _stream()), "stx_adam_step")
+
+
+class AdamPrepare:
+    """The first half of an Adam step (step counter + bias-corrected scalars into ws) for
+    conv_weight_compose16(adam_prepare=...) to run as a rider of the compose launch; done
+    tells the caller whether a launch took it (adam_step_prepared then, else adam_step)."""
+
+    def __init__(self, step_dev, ws, lr=1e-3, beta1=0.9, beta2=0.999):
+        self.step_dev, self.ws = step_dev, ws
+        self.lr, self.beta1, self.beta2 = float(lr), float(beta1), float(beta2)
+        self.done = False
+
+
+def adam_step_prepared(p, g, m, v, ws, beta1=0.9, beta2=0.999, eps=1e-8, clear=None):
+    """The Adam update alone, with the scalars an AdamPrepare rider left in ws for this step
+    (stx_adam_step_prepared); clear: a float32 device tensor zeroed by the same launch."""
+    if clear is not None:
+        _req(clear, "clear")
+    check(lib().stx_adam_step_prepared(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                                       p.numel(), float(beta1), float(beta2), float(eps),
+                                       ws.data_ptr(), _p(clear),
+                                       0 if clear is None else clear.numel(), _stream()),
+          "stx_adam_step_prepared")
 
 
 # ----------------------------------------------------------------------- instance norm

@@ -211,6 +211,7 @@ class LossState:
     grams: list = field(default_factory=lambda: [None] * 5)  # fused Gram partial slabs
     fin_jobs: list = None                       # the last batched finalize's jobs (bench)
     mse_parts: torch.Tensor = None              # content tap's fused MSE sums (2 per tile)
+    loss_job: object = None                     # deferred loss finalize (ops.LossFinalizeJob)
 
 
 def tap_weights(style_weight, layer_weights=None):
@@ -241,7 +242,7 @@ def _folded_style(style_weight, layer_weights):
 
 
 def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
-                 folded_weights=None, total=None, extra_slot=False):
+                 folded_weights=None, total=None, extra_slot=False, defer_loss=False):
     """Forward of all 7 losses for input batch x [B,3,H,W] given style targets and
     the content target c4 (= Z4 of the content image, pre-ReLU).
 
@@ -256,7 +257,12 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
 
     The five style-loss reductions are deferred (partials kept in per-layer
     workspaces) and done in one launch after the forward, together with the
-    weighted total (into `total`, if given, with the folded weights)."""
+    weighted total (into `total`, if given, with the folded weights).
+
+    defer_loss: that launch is not made here but recorded on the state (st.loss_job) for
+    loss_backward, which runs it -- as a rider block of its compose launch where it takes
+    that path, else as the launch it would have been -- so the losses and `total` are
+    written when loss_backward returns, not before.  Nothing in the backward reads them."""
     if st is None:
         st = LossState()
     dev = x.device
@@ -374,7 +380,11 @@ def loss_forward(feat: VGGFeatures, targets, x, c4, st: LossState | None = None,
         if extra_slot:  # st.losses[8] (written by the caller, e.g. TV) joins the total
             w += [0.0, 0.0, 1.0]
             extra = st.losses[5:9]
-    ops.loss_finalize(st.parts, st.losses[0:5], extra=extra, weights=w, total=total)
+    st.loss_job = ops.LossFinalizeJob(st.parts, st.losses[0:5], extra=extra, weights=w,
+                                      total=total)
+    if not defer_loss:
+        st.loss_job.launch()
+        st.loss_job = None
     return st
 
 
@@ -397,15 +407,27 @@ def loss_values(st: LossState):
 
 
 def loss_backward(feat: VGGFeatures, st: LossState, g=None, dx=None, feature_grad=True,
-                  scratch=None):
+                  scratch=None, adam_prepare=None):
     """dx = sum_i g[i] * d loss_i / dx (g: device [7]: style x5, content, feature), or,
     for a folded forward, the gradient of the folded weighted total (g ignored).
 
     Six launches: the Gram backward of the pooled layers runs as a 1x1 MFMA conv with
     the ReLU+MaxPool backward fused into its epilogue; the Gram backward of the
     other layers is a second GEMM phase inside the data-gradient conv, after its
-    ReLU mask."""
+    ReLU mask.
+
+    A loss finalize deferred by loss_forward(defer_loss=True) and adam_prepare (an
+    ops.AdamPrepare: the step counter and scalars of the Adam update that follows) ride on
+    the compose launch where this backward has one (split path, B == 1, conv3_1's
+    transposed slab present).  Otherwise the finalize is launched here as usual and
+    adam_prepare is left not done: the caller then takes the full ops.adam_step."""
     z = st.z
+    job, st.loss_job = st.loss_job, None
+    if job is not None and N.knob("STX_TAIL_LOSS", "1") == "0":
+        job.launch()  # (A/B: the launch of its own, where loss_forward made it)
+        job = None
+    if adam_prepare is not None and N.knob("STX_TAIL_ADAM", "1") == "0":
+        adam_prepare = None
     B = z[0].shape[0]
     sc = scratch if scratch is not None else {}
 
@@ -441,7 +463,7 @@ def loss_backward(feat: VGGFeatures, st: LossState, g=None, dx=None, feature_gra
         # B == 1.
         sc["compose5"] = ops.conv_weight_compose16(
             st.coef[4], ca[4], feat.w[4], feat.wtT16[4][1], slot(am, COMPOSE_AMAX_SLOT),
-            scale=s(4), out=sc.get("compose5"))
+            scale=s(4), out=sc.get("compose5"), loss_job=job, adam_prepare=adam_prepare)
         cout, cin = VGG_CONV_SHAPES[4]
         if up4:
             dz4 = ops.conv2d(z[4], None, cout, cin, 3, out=buf("dz4", z[3].shape),
@@ -452,6 +474,8 @@ def loss_backward(feat: VGGFeatures, st: LossState, g=None, dx=None, feature_gra
                              wt16=(sc["compose5"], slot(am, COMPOSE_AMAX_SLOT)),
                              in_amax=slot(am, 5))
     else:
+        if job is not None:
+            job.launch()
         # conv3_1 output: dZ5 = A5 Z5
         dz5 = ops.gram_bwd_fused(st.coef[4], z[4], out=buf("dz5", z[4].shape), acc_scale=s(4),
                                  out_amax=slot(am, 6), z_amax=slot(am, 5) if sp else None)
@@ -575,15 +599,22 @@ class GatysEngine:
         self.graph = None
 
     def _iteration(self):
+        # the loss finalize and Adam's step-counter launch (it depends on the previous step
+        # alone) ride on the backward's compose launch where it has one
         loss_forward(self.feat, self.targets, self.x, self.c4, self.st,
-                     folded_weights=(self.sw, self.cw), total=self.total)
+                     folded_weights=(self.sw, self.cw), total=self.total, defer_loss=True)
+        prep = ops.AdamPrepare(self.step_dev, self.adam_ws, self.lr, *self.betas)
         loss_backward(self.feat, self.st, dx=self.grad, feature_grad=False,
-                      scratch=self.scratch)
+                      scratch=self.scratch, adam_prepare=prep)
         if self.temporal is not None:
             _temporal_term(self)
         # the Adam launch also zeroes the amax groups for the next iteration's forward
-        ops.adam_step(self.x, self.grad, self.m, self.v, self.step_dev, self.adam_ws, self.lr,
-                      self.betas[0], self.betas[1], self.eps, clear=self.st.amax)
+        if prep.done:
+            ops.adam_step_prepared(self.x, self.grad, self.m, self.v, self.adam_ws,
+                                   self.betas[0], self.betas[1], self.eps, clear=self.st.amax)
+        else:
+            ops.adam_step(self.x, self.grad, self.m, self.v, self.step_dev, self.adam_ws,
+                          self.lr, self.betas[0], self.betas[1], self.eps, clear=self.st.amax)
         self.st.amax_cleared = True
 
     def retarget(self, content, init=None, temporal_ref=None, temporal_mask=None):
@@ -697,7 +728,7 @@ class GatysLBFGS:
 
     def _closure(self):
         loss_forward(self.feat, self.targets, self.x, self.c4, self.st,
-                     folded_weights=(self.sw, self.cw), total=self.total)
+                     folded_weights=(self.sw, self.cw), total=self.total, defer_loss=True)
         loss_backward(self.feat, self.st, dx=self.grad, feature_grad=False,
                       scratch=self.scratch)
         if self.temporal is not None:
