@@ -688,6 +688,68 @@ int stx_cin_mix(const stx_cin_job* jobs, int njobs, const float* mix, int n, int
 int stx_cin_param_grads(const stx_cin_job* jobs, int njobs, const float* mix, int n, int S,
                         void* stream);
 
+/* Adaptive instance normalisation (Huang & Belongie 2017, "Arbitrary Style Transfer in
+ * Real-time with Adaptive Instance Normalization"): a style given at conversion time.
+ * Planes are x [n][c][hw] fp32 with hw >= 2; statistics are per plane,
+ *   mean = sum x / hw,   std = sqrt(sum (x - mean)^2 / (hw - 1) + eps)
+ * (unbiased variance, eps inside the root: the paper's calc_mean_std, NOT the biased rstd
+ * of stx_instnorm_fwd).  The deviations are taken about the computed mean, in a second pass
+ * inside the block.  One block per plane and fixed-order reductions: bit-reproducible.
+ * Every entry point below forms the statistics with the same code under the same kernel
+ * selection (by hw, hw % 4 and the 16-byte alignment of x alone), so the same plane has the
+ * same mean / std bits whichever of them computed it.  No alignment contract: an unaligned
+ * x or an hw % 4 != 0 takes the loop kernels.  None of these allocates or synchronises;
+ * arguments are checked before any launch (STX_E_INVALID; hw >= 2, hw <= 2^30, n c < 2^31).
+ *
+ * stx_chan_stats: mean, std [n][c] of x, or with relu_input of (x <= 0 ? +0 : x), which
+ *   keeps a NaN as stx_relu_fwd does (a tap read from the conv output before its ReLU).
+ *   A NaN or Inf in a plane makes that plane's mean and std NaN; no other plane is touched.
+ *
+ * stx_adain: style statistics smean, sstd [S][c], mix [n][S], strength alpha:
+ *     M = sum_s mix[k][s] smean[s][ch],  G = sum_s mix[k][s] sstd[s][ch]   (fma chains from
+ *         0, s ascending, as stx_cin_mix: a one-hot row reproduces the table row's bits)
+ *     r = G / std,  a = fma(alpha, r, 1 - alpha),  b = alpha * fma(-r, mean, M)
+ *     y = fma(x, a, b)
+ *   alpha = 1 with a one-hot row is the paper's AdaIN; alpha = 0 gives a = 1, b = 0 and
+ *   y = x in value; a convex row is the paper's style interpolation (the blend is linear in
+ *   (smean, sstd)).  mean, std [n][c] (may be NULL) receive the content statistics, with
+ *   stx_chan_stats' bits.  out_amax (amax group, zeroed by the caller, may be NULL) receives
+ *   max|y|, the next split conv's input scale.  y may be x.  Planes of up to 65536 floats
+ *   with hw % 4 == 0 and an aligned x are read once.
+ *   A NaN or Inf in a plane of x, or a NaN in that plane's row of mix or channel of the
+ *   tables, makes its mean, std and every y of the plane NaN (at alpha = 0 too: b is
+ *   0 * NaN), and out_amax then holds a NaN; the other planes are untouched, bit for bit.
+ *
+ * stx_stats_loss: against targets tmean, tstd [n][c],
+ *     out[1] = weight / (n c) * sum_{n,c} (mean - tmean)^2,  out[2] likewise of the stds,
+ *     out[0] = out[1] + out[2];   *add_to += out[0] when add_to is given.
+ *   The per-plane squares go to the workspace and one block sums them in a fixed order.
+ *   mean, std [n][c] (may be NULL) are saved for the backward.  A NaN or Inf in any plane
+ *   makes that plane's saved mean and std NaN and all of out NaN; the other planes' saved
+ *   statistics are untouched, bit for bit.
+ *
+ * stx_stats_loss_bwd: from the saved mean, std,
+ *     dx_i (+)= A + B (x_i - mean),  A = kk 2 (mean - tmean) / hw,
+ *     B = kk 2 (std - tstd) / ((hw - 1) std),  kk = weight / (n c) * (*g_dev or 1),
+ *   formed as fma(B, x_i - mean, A): one streaming pass, A and B once per block.  With
+ *   accumulate the term is added to dx, and where the term is 0 the old value stays bit for
+ *   bit (a tap's gradient joins the one arriving from deeper layers without another pass).
+ *   out_amax (may be NULL) receives max|dx| as stored.  A plane whose saved statistics are
+ *   NaN gets a NaN dx throughout; a NaN x_i alone (statistics given from elsewhere) makes
+ *   that element NaN; the other planes are untouched, bit for bit. */
+int stx_chan_stats(const float* x, float* mean, float* std_, int n, int c, int hw, float eps,
+                   int relu_input, void* stream);
+int stx_adain(const float* x, const float* smean, const float* sstd, const float* mix,
+              float alpha, float* y, float* mean, float* std_, int n, int c, int hw, int S,
+              float eps, float* out_amax, void* stream);
+size_t stx_stats_loss_ws(int n, int c);
+int stx_stats_loss(const float* x, const float* tmean, const float* tstd, int n, int c, int hw,
+                   float eps, float weight, float* out, float* add_to, float* mean, float* std_,
+                   void* ws, size_t ws_bytes, void* stream);
+int stx_stats_loss_bwd(const float* x, const float* mean, const float* std_, const float* tmean,
+                       const float* tstd, int n, int c, int hw, float weight, const float* g_dev,
+                       float* dx, int accumulate, float* out_amax, void* stream);
+
 /* nearest x2 upsample: y [nc][2h][2w];  backward dx[y][x] = sum of dy's 2x2 block */
 int stx_upsample2x_fwd(const float* x, float* y, int nc, int h, int w, void* stream);
 int stx_upsample2x_bwd(const float* dy, float* dx, int nc, int h, int w, void* stream);

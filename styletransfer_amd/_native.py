@@ -220,6 +220,11 @@ SIGNATURES = {
                                i32, i32, vp, vp, sz, vp]),
     "stx_cin_mix": (i32, [C.POINTER(CinJob), i32, vp, i32, i32, vp]),
     "stx_cin_param_grads": (i32, [C.POINTER(CinJob), i32, vp, i32, i32, vp]),
+    "stx_chan_stats": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, vp]),
+    "stx_adain": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp]),
+    "stx_stats_loss_ws": (sz, [i32, i32]),
+    "stx_stats_loss": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]),
+    "stx_stats_loss_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, i32, vp, vp]),
     "stx_upsample2x_fwd": (i32, [vp, vp, i32, i32, i32, vp]),
     "stx_upsample2x_bwd": (i32, [vp, vp, i32, i32, i32, vp]),
     "stx_tv_ws": (sz, [i32, i32, i32, i32]),

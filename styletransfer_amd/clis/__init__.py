@@ -1,7 +1,7 @@
 """`python -m stransfer` command groups (mirror of stransfer/clis/__init__.py)."""
 import click
 
-from . import fast_st, gatys_guided, gatys_st, gatys_video, video_st
+from . import adain, fast_st, gatys_guided, gatys_st, gatys_video, video_st
 
 
 @click.group(commands={
@@ -10,6 +10,7 @@ from . import fast_st, gatys_guided, gatys_st, gatys_video, video_st
     "gatys_st": gatys_st.gatys_st,
     "gatys_guided": gatys_guided.gatys_guided,
     "gatys_video": gatys_video.gatys_video,
+    "adain": adain.adain,
 })
 def cli():
     """Style Transfer (MI355X)"""

@@ -24,6 +24,7 @@ __all__ = [
     "maxpool2x2", "maxpool2x2_bwd", "relupool_bwd", "relu", "relu_bwd", "adam_step",
     "instnorm_fwd", "instnorm_bwd", "cin_mix", "upsample2x", "upsample2x_bwd", "tv_loss",
     "temporal_loss", "temporal_loss_bwd", "flow_warp", "flow_consistency", "flow_compose", "masked_mse",
+    "chan_stats", "adain", "stats_loss", "stats_loss_bwd",
     "color_stats", "color_affine", "resample_plan",
     "resample2d",
     "flow_pyramid", "flow_luma", "flow_linearize", "flow_jacobi", "flow_scale",
@@ -1430,6 +1431,110 @@ def masked_mse(x, ref, mask, weight, out=None, add_to=None, grad=None, accumulat
                            float(weight), out.data_ptr(), _p(add_to), _p(grad),
                            int(bool(accumulate)), wp, wn, _stream()), "stx_masked_mse")
     return out
+
+
+# ------------------------------------------------- adaptive instance norm (arbitrary style)
+def _planes(x, name="x"):
+    _req(x, name)
+    if x.dim() < 3:
+        raise N.NativeError(f"{name}: [n, c, ...] planes required (got {tuple(x.shape)})")
+    n, c = x.shape[:2]
+    return n, c, x[0, 0].numel()
+
+
+def _nc(t, n, c, name):
+    if t is not None and (_req(t, name).numel() != n * c):
+        raise N.NativeError(f"{name}: [{n}][{c}] required (got {tuple(t.shape)})")
+    return t
+
+
+def chan_stats(x, eps=1e-5, relu_input=False):
+    """(mean, std) [n, c] of the planes of x (stx_chan_stats): unbiased variance, eps inside
+    the root; relu_input takes them of max(x, 0) with a NaN kept."""
+    n, c, hw = _planes(x)
+    mean = torch.empty(n, c, device=x.device, dtype=torch.float32)
+    std = torch.empty_like(mean)
+    check(lib().stx_chan_stats(x.data_ptr(), mean.data_ptr(), std.data_ptr(), n, c, hw,
+                               float(eps), int(bool(relu_input)), _stream()), "stx_chan_stats")
+    return mean, std
+
+
+def adain(x, smean, sstd, mix, alpha=1.0, eps=1e-5, out=None, out_amax=None, stats=False):
+    """y = fma(x, a, b) per plane (stx_adain): style tables smean, sstd [S, c], mix [n, S],
+    strength alpha.  stats=True also returns the content (mean, std) [n, c]."""
+    n, c, hw = _planes(x)
+    _req(smean, "smean")
+    _req(sstd, "sstd")
+    _req(mix, "mix")
+    if smean.dim() != 2 or smean.shape[1] != c or sstd.shape != smean.shape:
+        raise N.NativeError(f"smean, sstd: equal [S][{c}] required (got {tuple(smean.shape)}, "
+                            f"{tuple(sstd.shape)})")
+    S = smean.shape[0]
+    if tuple(mix.shape) != (n, S):
+        raise N.NativeError(f"mix: [{n}][{S}] required (got {tuple(mix.shape)})")
+    if out is None:
+        out = torch.empty_like(x)
+    elif _req(out, "out").shape != x.shape:
+        raise N.NativeError(f"out: the shape of x required (got {tuple(out.shape)})")
+    mean = std = None
+    if stats:
+        mean = torch.empty(n, c, device=x.device, dtype=torch.float32)
+        std = torch.empty_like(mean)
+    check(lib().stx_adain(x.data_ptr(), smean.data_ptr(), sstd.data_ptr(), mix.data_ptr(),
+                          float(alpha), out.data_ptr(), _p(mean), _p(std), n, c, hw, S,
+                          float(eps), _p(out_amax), _stream()), "stx_adain")
+    return (out, mean, std) if stats else out
+
+
+def stats_loss(x, tmean, tstd, weight=1.0, eps=1e-5, out=None, add_to=None, save=True):
+    """out[0] = weight / (n c) * sum [(mean - tmean)^2 + (std - tstd)^2], out[1] / out[2] the
+    two parts (stx_stats_loss); returns (out, mean, std) with the statistics saved for
+    stats_loss_bwd (None, None with save=False)."""
+    n, c, hw = _planes(x)
+    _nc(tmean, n, c, "tmean")
+    _nc(tstd, n, c, "tstd")
+    if tmean is None or tstd is None:
+        raise N.NativeError("tmean, tstd required")
+    if out is None:
+        out = torch.empty(3, device=x.device, dtype=torch.float32)
+    elif _req(out, "out").numel() < 3:
+        raise N.NativeError("out: 3 floats required")
+    if add_to is not None:
+        _req(add_to, "add_to")
+    mean = std = None
+    if save:
+        mean = torch.empty(n, c, device=x.device, dtype=torch.float32)
+        std = torch.empty_like(mean)
+    L = lib()
+    wp, wn = _scratch().get(L.stx_stats_loss_ws(n, c), x.device)
+    check(L.stx_stats_loss(x.data_ptr(), tmean.data_ptr(), tstd.data_ptr(), n, c, hw, float(eps),
+                           float(weight), out.data_ptr(), _p(add_to), _p(mean), _p(std), wp, wn,
+                           _stream()), "stx_stats_loss")
+    return out, mean, std
+
+
+def stats_loss_bwd(x, mean, std, tmean, tstd, weight=1.0, g_dev=None, dx=None, accumulate=False,
+                   out_amax=None):
+    """dx (+)= d stats_loss / dx scaled by *g_dev (stx_stats_loss_bwd), from the forward's
+    saved mean, std.  accumulate needs dx."""
+    n, c, hw = _planes(x)
+    for t, nm in ((mean, "mean"), (std, "std"), (tmean, "tmean"), (tstd, "tstd")):
+        if t is None:
+            raise N.NativeError(f"{nm} required")
+        _nc(t, n, c, nm)
+    if g_dev is not None:
+        _req(g_dev, "g_dev")
+    if dx is None:
+        if accumulate:
+            raise N.NativeError("accumulate: dx required")
+        dx = torch.empty_like(x)
+    elif _req(dx, "dx").shape != x.shape:
+        raise N.NativeError(f"dx: the shape of x required (got {tuple(dx.shape)})")
+    check(lib().stx_stats_loss_bwd(x.data_ptr(), mean.data_ptr(), std.data_ptr(),
+                                   tmean.data_ptr(), tstd.data_ptr(), n, c, hw, float(weight),
+                                   _p(g_dev), dx.data_ptr(), int(bool(accumulate)),
+                                   _p(out_amax), _stream()), "stx_stats_loss_bwd")
+    return dx
 
 
 # ---------------------------------------------------------------------- colour control
