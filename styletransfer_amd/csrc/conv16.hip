@@ -363,13 +363,22 @@ __device__ __forceinline__ void phase2_pre(f32x16 (&acc)[2][2], const stx_conv_p
 //     hi / lo MFMA, N-tile dx / lane l32 <-> pixel (2 (ty0 + wn) + dy, 2 (tx0 + l32) + dx),
 //     so the lane's N-tile element sits under its own element of d.  z in chunks of 16
 //     channels through double-buffered LDS ([P][cg][dx][row][32] 16-B units: the
-//     fragment reads are conflict-free), one barrier per chunk; A' straight from L2 into
-//     fragment registers (as phase2_pre); accumulators separate from acc, so each term
-//     keeps its own power-of-two scale;
+//     fragment reads are conflict-free), one barrier per chunk; A' (this block's 64
+//     columns, all C rows) is scaled and split once into LDS behind the z buffers and its
+//     fragments are read from there; accumulators separate from acc, so each term keeps
+//     its own power-of-two scale;
 //  3. y = A.z + the routed d, written as 8-B (dx pair) stores; max|y| -> out_amax.
+// The schedule: step 1 depends on z alone, so it runs INSIDE the conv's K loop (the kernel's
+// win_load / win_reduce): local chunk c issues the 8 window loads of four accumulator
+// elements behind its first step's halo / weight loads and folds them into sel[] one step
+// later, while the MFMA pipe works on the conv -- the windows are z's first trip from HBM,
+// and step 2 then finds it in L2.  Slices the loop is too short for (cin < 128) run after
+// it.  In the K2 form group g takes the elements i = g and hands its sel bits to group 0
+// with its accumulators.  This function is steps 2 and 3, given sel[].
 template <int TW>
 __device__ __forceinline__ void epi_unpool_gram(f32x16 (&acc)[2][1], const stx_conv_params& p,
-                                                const EpiTile& t, float descale, char* smem) {
+                                                const EpiTile& t, float descale, char* smem,
+                                                const uint32_t (&sel)[4]) {
   static_assert(TW == 32, "32 x 4 tiles of d");
   constexpr int UNITS = 2 * 2 * 2 * 128;  // [P][cg][dx][4 rows x 32]: one 16 KB buffer
   const int tid = threadIdx.x, h = t.h, l32 = t.l32, wn = t.wn;
@@ -378,40 +387,28 @@ __device__ __forceinline__ void epi_unpool_gram(f32x16 (&acc)[2][1], const stx_c
   const uint32_t pb2 = (uint32_t)H2 * (uint32_t)W2 * 4u;
   const size_t img = (size_t)t.n * C * H2 * W2, blk = img + (size_t)t.co0 * H2 * W2;
   const auto rz = make_srd(p.up_z + img, (uint32_t)C * pb2);   // all channels (A . z)
-  const auto rw = make_srd(p.up_z + blk, 64u * pb2);           // this block's 64 (windows)
   const auto ry = make_srd(p.y + blk, 64u * pb2);
   const auto rx = make_srd(p.aux ? p.aux + blk : p.y + blk, p.aux ? 64u * pb2 : 0u);
   const int Y0 = 2 * (t.ty0 + wn), X0 = 2 * (t.tx0 + l32);
   const uint32_t win = (uint32_t)(Y0 * W2 + X0) * 4u, wrow = (uint32_t)W2 * 4u;
-  auto corow = [&](int i, int r) { return i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h; };
-  // 1. window first maximum and mask
-  uint32_t sel[4] = {0u, 0u, 0u, 0u};
-#pragma unroll 1
-  for (int i = 0; i < 2; ++i) {
-    f32x2_t top[16], bot[16];
+#if defined(STX_DIAG_UNPOOL_END) && STX_DIAG_UNPOOL_END == 1
+  // timing-only diagnostic build (make DIAG=1 UNPOOL_END=1, numerically meaningless): the
+  // conv and a plain store of d into the head of each output plane -- no window, no A.z
+  const uint32_t po = (uint32_t)((t.ty0 + wn) * p.wo + t.tx0 + l32) * 4u;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const uint32_t o = (uint32_t)corow(i, r) * pb2 + win;
-      top[r] = buf_ld2(rw, o);
-      bot[r] = buf_ld2(rw, o + wrow);
-    }
+  for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float z0 = top[r].x, z1 = top[r].y, z2 = bot[r].x, z3 = bot[r].y;
-      const float r0 = relu_bits(z0), r1 = relu_bits(z1), r2 = relu_bits(z2), r3 = relu_bits(z3);
-      int bi = 0;
-      float best = r0;
-      if (r1 > best) { best = r1; bi = 1; }
-      if (r2 > best) { best = r2; bi = 2; }
-      if (r3 > best) { bi = 3; }
-      const float zs = bi == 0 ? z0 : bi == 1 ? z1 : bi == 2 ? z2 : z3;
-      const uint32_t bit = zs > 0.f ? 1u << (16 * i + r) : 0u;
-      sel[0] |= bi == 0 ? bit : 0u;
-      sel[1] |= bi == 1 ? bit : 0u;
-      sel[2] |= bi == 2 ? bit : 0u;
-      sel[3] |= bi == 3 ? bit : 0u;
-    }
-  }
+    for (int r = 0; r < 16; ++r)
+      __builtin_amdgcn_raw_buffer_store_b32(
+          __float_as_uint(acc[i][0][r] * descale), ry,
+          (uint32_t)(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * pb2 + po, 0, 0);
+  return;
+#endif
+#if defined(STX_DIAG_UNPOOL_END) && STX_DIAG_UNPOOL_END == 2
+  constexpr bool AZ = false;  // (make DIAG=1 UNPOOL_END=2: the unpool routing without A.z)
+#else
+  constexpr bool AZ = true;
+#endif
   // 2. scales: A' = s2 A 2^(15 - ea), z' = z 2^(15 - ez); A.z = acc2 2^(ea + ez - 30)
   const float s2 = p.p2_scale ? *p.p2_scale : 1.f;
   const int ea = amax_exp(read_amax(p.p2_wt_amax) * fabsf(s2));
@@ -422,7 +419,7 @@ __device__ __forceinline__ void epi_unpool_gram(f32x16 (&acc)[2][1], const stx_c
   // [chunk][P][cg][co] 16-B units (8 channels of one cout), C x 256 B; thread t -> the
   // units (channel group of 8, cout) t, t + 256, ...
   char* la = smem + 2 * UNITS * 16;
-  {
+  if constexpr (AZ) {
     const float* __restrict__ A = p.p2_wt + (size_t)t.n * p.p2_wt_batch_stride + t.co0;
     for (int u = tid; u < C * 8; u += 256) {
       const int co = u & 63, cg8 = u >> 6;  // channel group of 8
@@ -477,11 +474,13 @@ __device__ __forceinline__ void epi_unpool_gram(f32x16 (&acc)[2][1], const stx_c
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc2[dx][i][r] = 0.f;
     f32x2_t g[8];
-    fetch(dy, 0, g);
-    __syncthreads();  // the LDS is free (main loop / the previous pass's reads done)
-    stage(g, 0);
-    fetch(dy, 16, g);
-    for (int c = 0; c < nch; ++c) {
+    if constexpr (AZ) {
+      fetch(dy, 0, g);
+      __syncthreads();  // the LDS is free (main loop / the previous pass's reads done)
+      stage(g, 0);
+      fetch(dy, 16, g);
+    }
+    for (int c = 0; AZ && c < nch; ++c) {
       const int b = c & 1;
       __syncthreads();  // buffer b (and A') complete; buffer b ^ 1's reads (chunk c - 1) done
       const char* lz = smem + b * UNITS * 16;
@@ -510,7 +509,11 @@ __device__ __forceinline__ void epi_unpool_gram(f32x16 (&acc)[2][1], const stx_c
     }
     // 3. y = A.z (+ aux_scale aux) + the routed d (8-B stores of the dx pair); the aux
     // loads all go out before the first store (vmcnt counts stores too)
+    // (the lane's part of an offset in one register, the element's channel row -- uniform
+    // -- as the scalar offset: no per-element address registers held across the pass)
     const uint32_t sel0 = dy ? sel[2] : sel[0], sel1 = dy ? sel[3] : sel[1];
+    const uint32_t vo = (uint32_t)(4 * h) * pb2 + win + (uint32_t)dy * wrow;
+    auto so = [&](int i, int r) { return (uint32_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * pb2; };
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -519,7 +522,8 @@ __device__ __forceinline__ void epi_unpool_gram(f32x16 (&acc)[2][1], const stx_c
       if (p.aux) {
 #pragma unroll
         for (int r = rh; r < rh + 8; ++r)
-          xv[r] = buf_ld2(rx, (uint32_t)corow(i, r) * pb2 + win + (uint32_t)dy * wrow);
+          xv[r] = __builtin_bit_cast(
+              f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(rx, vo, so(i, r), 0));
       }
 #pragma unroll
       for (int r = rh; r < rh + 8; ++r) {
@@ -535,8 +539,7 @@ __device__ __forceinline__ void epi_unpool_gram(f32x16 (&acc)[2][1], const stx_c
                                  __float_as_uint(v1) & 0x7fffffffu));
         typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
         const u32x2_t dv = {__float_as_uint(v0), __float_as_uint(v1)};
-        __builtin_amdgcn_raw_buffer_store_b64(
-            dv, ry, (uint32_t)corow(i, r) * pb2 + win + (uint32_t)dy * wrow, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(dv, ry, vo, so(i, r), 0);
       }
     }
   }
@@ -851,8 +854,9 @@ struct C16up {
 // K2: two groups of four waves per block (512 threads) walk alternate 16-channel chunks of
 // the same tile with their own double-buffered halo / weight images and accumulators --
 // two waves per SIMD in a grid of one block per CU (the unpool launch of conv3_1^T at
-// B = 1); group 1 hands its sums to group 0 through LDS (acc0 + acc1, fixed order) and
-// ends, group 0 runs the epilogue (waves that have ended are not counted at a barrier).
+// B = 1); group 1 hands its sums and its half of the unpool window bits to group 0 through
+// LDS (acc0 + acc1, fixed order) and ends, group 0 runs the epilogue (waves that have ended
+// are not counted at a barrier).
 template <int TW, int LM, int P2, int NI, int WM = 1, bool K2 = false>
 __global__ void __launch_bounds__(256 * WM * (K2 ? 2 : 1),
                                   (WM == 2 || K2) ? 1 : ((NI == 1 && TW <= 32 && P2 == 0) ? 3 : 2))
@@ -872,7 +876,8 @@ conv3x3_f16x3_v2_kernel(stx_conv_params p, int tiles_x, int ntiles) {
                 "the unpool epilogue takes 32 x 4 tiles of a raw-input conv");
   static_assert(P2 != 2, "1x1 mode: v1 kernel");
   static_assert(WM == 1 || P2 == 0, "WM = 2: plain epilogue only");
-  static_assert(!K2 || (WM == 1 && !PAR && !UPP), "K2: the plain 4-wave loop");
+  static_assert(!K2 || (WM == 1 && !PAR && !UPP && P2 == 4),
+                "K2: the plain 4-wave loop of the unpool launch");
   constexpr int BM = C::BM;
   constexpr int NG = K2 ? 2 : 1;  // chunk groups
   constexpr int LDSB = NG * C::LOOP_BYTES > C::LDS_BYTES ? NG * C::LOOP_BYTES : C::LDS_BYTES;
@@ -1045,6 +1050,53 @@ conv3x3_f16x3_v2_kernel(stx_conv_params p, int tiles_x, int ntiles) {
 #pragma unroll
     for (int q = 0; q < C::NWU; ++q)
       *reinterpret_cast<f32x4*>(wbp + (tid + q * NT) * 16) = wreg[q];
+  };
+
+  // P2 = 4: the unpool epilogue's window pass (epi_unpool_gram, step 1) in slices of four
+  // accumulator elements, slice q = 4 i + r / 4 <-> (i, r = 4 (q & 3) + j), j = 0 .. 3: the
+  // 2x2 window of z over the lane's pixel of d in channel co0 + corow(i, r) as two 8-B loads;
+  // its first maximum of relu(z) (strict >, slot order 0..3) and the ReLU mask of the
+  // selected raw z -> bit 16 i + r of sel[slot].  K2: group g takes i = g.
+  constexpr int NQ = K2 ? 4 : 8;  // slices of this group
+  const int q0 = K2 ? 4 * gk : 0;
+  [[maybe_unused]] const uint32_t wpb = (uint32_t)(2 * p.ho) * (uint32_t)(2 * p.wo) * 4u;
+  [[maybe_unused]] const uint32_t wrow2 = (uint32_t)(2 * p.wo) * 4u;
+  [[maybe_unused]] const auto rwin =
+      make_srd(P2 == 4 ? p.up_z + ((size_t)n * p.cout + co0) * (size_t)(wpb / 4u) : p.x,
+               P2 == 4 ? 64u * wpb : 0u);
+  [[maybe_unused]] uint32_t sel[4] = {0u, 0u, 0u, 0u};
+  [[maybe_unused]] f32x2_t wtop[4], wbot[4];  // the slice in flight across a loop step
+  [[maybe_unused]] auto win_load = [&](int q, f32x2_t (&top)[4], f32x2_t (&bot)[4]) {
+    // (the lane's part of the offset in one register; the slice's channel row, uniform,
+    // as the scalar offset)
+    const uint32_t vo = (uint32_t)(4 * h) * wpb +
+                        (uint32_t)(2 * (ty0 + wn) * 2 * p.wo + 2 * (tx0 + l32)) * 4u;
+    const uint32_t so = (uint32_t)((q >> 2) * 32 + 8 * (q & 3)) * wpb;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      top[j] = __builtin_bit_cast(
+          f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(rwin, vo, so + (uint32_t)j * wpb, 0));
+      bot[j] = __builtin_bit_cast(
+          f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(rwin, vo + wrow2, so + (uint32_t)j * wpb, 0));
+    }
+  };
+  [[maybe_unused]] auto win_reduce = [&](int q, const f32x2_t (&top)[4], const f32x2_t (&bot)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float z0 = top[j].x, z1 = top[j].y, z2 = bot[j].x, z3 = bot[j].y;
+      const float r0 = relu_bits(z0), r1 = relu_bits(z1), r2 = relu_bits(z2), r3 = relu_bits(z3);
+      int bi = 0;
+      float best = r0;
+      if (r1 > best) { best = r1; bi = 1; }
+      if (r2 > best) { best = r2; bi = 2; }
+      if (r3 > best) { bi = 3; }
+      const float zs = bi == 0 ? z0 : bi == 1 ? z1 : bi == 2 ? z2 : z3;
+      const uint32_t bit = zs > 0.f ? 1u << (4 * q + j) : 0u;
+      sel[0] |= bi == 0 ? bit : 0u;
+      sel[1] |= bi == 1 ? bit : 0u;
+      sel[2] |= bi == 2 ? bit : 0u;
+      sel[3] |= bi == 3 ? bit : 0u;
+    }
   };
 
   // per-lane operand bases (bytes) relative to buffer 0
@@ -1226,6 +1278,13 @@ conv3x3_f16x3_v2_kernel(stx_conv_params p, int tiles_x, int ntiles) {
 #pragma unroll
               for (int r = (k + 1) % 3; r < C::NIT; r += 3) ld_halo(cn, r);
             }
+            if constexpr (P2 == 4) {
+              // slice q0 + c of the window pass: its loads behind this chunk's first
+              // step's (a wait for those does not wait for these), folded into sel[] one
+              // step later, after that step's staging
+              if (k == 0 && c < NQ) win_load(q0 + c, wtop, wbot);
+              if (k == 1 && c < NQ) win_reduce(q0 + c, wtop, wbot);
+            }
             __builtin_amdgcn_sched_barrier(0);
           }
           if (tl + 1 < 3) {
@@ -1238,10 +1297,27 @@ conv3x3_f16x3_v2_kernel(stx_conv_params p, int tiles_x, int ntiles) {
         __syncthreads();  // this step's reads done; the staged buffers are complete
       }
     }
+    if constexpr (P2 == 4) {
+      // the slices of the window pass the loop did not reach (fewer than NQ chunks), four
+      // slices' loads in flight at a time
+#pragma unroll 1
+      for (int qb = min(nchunks, NQ); qb < NQ; qb += 4) {
+        f32x2_t top[4][4], bot[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (qb + u < NQ) win_load(q0 + qb + u, top[u], bot[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (qb + u < NQ) win_reduce(q0 + qb + u, top[u], bot[u]);
+      }
+    }
     if constexpr (K2) {
-      // group 1's accumulators -> LDS (the loop buffers are dead after its last barrier),
-      // group 0 adds them; group 1 ends here
+      // group 1's accumulators and sel words (its elements i = 1) -> LDS (the loop buffers
+      // are dead after its last barrier), group 0 adds / ORs them; group 1 ends here
+      constexpr int GA = 4 * 2 * NI * 16 * 64;  // floats of a group's accumulators
       float* red = reinterpret_cast<float*>(smem);
+      u32x4_t* sx = reinterpret_cast<u32x4_t*>(smem + GA * 4);  // [tid]
+      static_assert(GA * 4 + 256 * 16 <= LDSB, "K2 hand-off fits");
       if (gk == 1) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -1249,6 +1325,7 @@ conv3x3_f16x3_v2_kernel(stx_conv_params p, int tiles_x, int ntiles) {
           for (int j = 0; j < NI; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) red[(((wave * 2 + i) * NI + j) * 16 + r) * 64 + lane] = acc[i][j][r];
+        sx[tid] = u32x4_t{sel[0], sel[1], sel[2], sel[3]};
       }
       __syncthreads();
       if (gk == 1) return;
@@ -1258,6 +1335,9 @@ conv3x3_f16x3_v2_kernel(stx_conv_params p, int tiles_x, int ntiles) {
         for (int j = 0; j < NI; ++j)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[i][j][r] += red[(((wave * 2 + i) * NI + j) * 16 + r) * 64 + lane];
+      const u32x4_t so = sx[tid];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) sel[s] |= so[s];
       __syncthreads();  // (the epilogue reuses this LDS)
     }
 
@@ -1278,7 +1358,7 @@ conv3x3_f16x3_v2_kernel(stx_conv_params p, int tiles_x, int ntiles) {
       // (eligibility: stx_conv2d -- stx_conv_params.unpool_out)
       static_assert(2 * 2 * 2 * 2 * 128 * 16 + 128 * 256 <= C::LDS_BYTES,
                     "unpool epilogue buffers fit");
-      epi_unpool_gram<TW>(acc, p, et, descale, smem);
+      epi_unpool_gram<TW>(acc, p, et, descale, smem, sel);
     } else if constexpr (P2 == 3) {
       // (eligibility: launch16v2 -- data gradient + mask + the phase, bias / out_amax only)
       const int ez = amax_exp(read_amax(p.p2_amax));

@@ -449,7 +449,9 @@ def loss_backward(feat: VGGFeatures, st: LossState, g=None, dx=None, feature_gra
     # conv that produces dP2 (stx_conv_params.unpool_out): dP2 never reaches HBM
     dz4 = None
     up4 = None
+    # (an odd Z4 -- the floored pool drops its last row / column -- takes the streaming path)
     if sp and ca[3] is not None and n4[3] % 32 == 0 and n4[2] % 4 == 0 and \
+            tuple(z[3].shape[2:]) == (2 * n4[2], 2 * n4[3]) and \
             N.knob("STX_UNPOOL_FUSE", "1") != "0":
         up4 = dict(unpool_out=(z[3], st.coef[3], ca[3], slot(am, 4), s(3)),
                    aux=st.c4 if folded else None, aux_scale=-st.alpha,
@@ -504,6 +506,7 @@ def loss_backward(feat: VGGFeatures, st: LossState, g=None, dx=None, feature_gra
     # -> grad wrt pool(relu Z2)
     n2 = (B, 64, z[1].shape[2] // 2, z[1].shape[3] // 2)
     if sp and ca[1] is not None and n2[3] % 32 == 0 and n2[2] % 4 == 0 and \
+            tuple(z[1].shape[2:]) == (2 * n2[2], 2 * n2[3]) and \
             N.knob("STX_UNPOOL_FUSE", "1") != "0":
         # dZ2 = unpool(dP1) [Z2 > 0] + A2 Z2 in conv2_1^T's epilogue: dP1 never reaches HBM
         dz2 = feat.dgrad(2, dz3, buf("dz2", z[1].shape), in_amax=slot(am, 8),
